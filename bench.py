@@ -14,13 +14,20 @@ G_unet_mha_vit_efficient true).  A step = set_input(device-resident batch) + opt
 (forward, backward, gradient all-reduce, fused AdamW + EMA, refresh of the bf16 weights).
 
 Default run: 50 timed steps; `ms_per_step` / `value` follow the contract (K steps / total time, max over ranks),
-`ms_per_step_median` is the median of the per-step HIP-event times of the same region.  With the default flags (N = 1, palette) the
-line also carries a `cut` object: the CUT G+D step of BASELINE configs[2] (SegFormer-attn G + [projected_d, basic] D + MoNCE,
-256x256, batch 16) measured in the same process right after the palette leg, with its own roofline and CPU baseline, and the objects
-`c4_512` (configs[3]: DDPM UNet 512x512, batch 8) and `cm` (configs[4]: consistency-model step 256x256, batch 64): value, ms per step,
-fraction of the MFMA peak.
+`ms_per_step_median` is the median of the per-step HIP-event times of the same region.  A plain run does only that: set-up, warm-up,
+the K timed steps, `--dump-outputs DIR` if given, and the JSON line.
 
-Extra objects on the JSON line:
+`--dump-outputs DIR` writes what the timed step computes (the losses, and a fixed seeded sample of the trained parameters, their EMA
+copy and Adam's first moment) as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs: after the timed
+steps the model is built again from its seeded initial state and the same step runs DUMP_STEPS times on the same batch (see dump_outputs).
+
+`--full` adds everything else, each part still switchable off (--no-kernel-timing, --no-cpu-baseline, --no-cut-leg): the `roofline` and
+`cpu_baseline` objects below and, with N = 1 and palette, a `cut` object: the CUT G+D step of BASELINE configs[2] (SegFormer-attn G +
+[projected_d, basic] D + MoNCE, 256x256, batch 16) measured right after the palette leg, with its own roofline and CPU baseline, and the
+objects `c4_512` (configs[3]: DDPM UNet 512x512, batch 8) and `cm` (configs[4]: consistency-model step 256x256, batch 64): value, ms per
+step, fraction of the MFMA peak.
+
+Extra objects on the JSON line of a `--full` run:
   roofline     -- dominant kernel = the one with the largest summed time (conv3x3_halo_kernel: halo-resident
                   implicit-GEMM 3x3 convolution, forward + input-gradient):
                   achieved = algorithmic FLOPs per launch (2*M*N*K) / average launch duration, both
@@ -508,6 +515,49 @@ def emit(line):
     print(out, flush=True)
 
 
+DUMP_SAMPLE = 1 << 21      # entries per sampled array of --dump-outputs: 8 MB of float32 each
+# --dump-outputs replays the timed step this many times from the seeded initial state: step 1 creates the EMA copy, step 2 is the steady-state
+# step (fused AdamW with running moments + EMA).  The step's fp32 sums are taken in whatever order the workgroups retire, and
+# Adam's normalised update turns that rounding into a different trajectory within a few steps: two processes agree to float32 rounding after
+# 2 steps from the same state (largest difference below 1e-7 on parameters of order 1) but not after the W + K steps of a timed run
+DUMP_STEPS = 2
+
+
+def replay_for_dump(args, rank, local_rank, world, batch):
+    """the model built again from its seeded initial state (build_model seeds the weights and the device RNG the step draws t / noise
+    from), then DUMP_STEPS calls of the timed step on the timed batch: identical inputs in every run, so identical outputs up to rounding"""
+    model, _ = build_model(args, rank, local_rank, world)
+    for _ in range(DUMP_STEPS):
+        model.set_input(batch)
+        model.optimize_parameters()
+    torch.cuda.synchronize()
+    return model
+
+
+def dump_outputs(model, out_dir):
+    """--dump-outputs DIR: what the step handed its caller (the model of replay_for_dump).  loss_<name>.npy (float64 scalar) per current
+    loss; params.npy, params_ema.npy and adam_exp_avg.npy (float32): the trained parameters, their EMA copy and Adam's first moment (the
+    running average the step's gradients went into), each the same seeded sample of DUMP_SAMPLE entries out of every network's parameters
+    taken in module order and logical layout, so that the sample does not depend on how the arena lays them out."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in model.get_current_losses().items():
+        np.save(os.path.join(out_dir, f"loss_{name}.npy"), np.float64(float(v.detach() if torch.is_tensor(v) else v)))
+    arenas = [model._net(n).arena for n in model.model_names]
+    flats = {"params": [a.p for a in arenas], "adam_exp_avg": [a.m for a in arenas]}
+    if all(a.ema is not None for a in arenas):
+        flats["params_ema"] = [a.ema for a in arenas]
+    idx = None
+    for key, fl in flats.items():
+        v = torch.cat([t.reshape(-1) for a, f in zip(arenas, fl) for t in a.named_views(f).values()])
+        if idx is None:
+            n = v.numel()
+            pick = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+            idx = torch.from_numpy(pick).to(v.device)
+        np.save(os.path.join(out_dir, key + ".npy"), v[idx].float().cpu().numpy())
+
+
 def leg_subprocess(name, no_cpu, timeout_s=420):
     """One extra leg of the default line in its OWN process: every leg starts from an empty allocator (in one process the legs inherited
     each other's 100+ GB of cached blocks, and one step in ten of the 512x512 leg stalled for ~2 s in hipMalloc), and a leg that dies
@@ -548,8 +598,14 @@ def main():
     ap.add_argument("--force-exchange", action="store_true", help="dev: run the multi-GPU gradient exchange path on one GPU (1-rank RCCL group)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--leg", default="", help=argparse.SUPPRESS)      # child mode: run ONE extra leg of the default line (cut | c4_512 | cm), print its JSON object
-    ap.add_argument("--dump-kernel-timing", default="", help="write the per-shape conv kernel timing table here")
+    ap.add_argument("--dump-kernel-timing", default="", help="--full only: write the per-shape conv kernel timing table here")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline number does not need: the dominant-kernel roofline pass, "
+                         "the CPU baseline and (N = 1, palette) the cut / cut_effnet / c4_512 / cm legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed step computes from the seeded "
+                         "initial state in DUMP_STEPS steps (losses; a seeded sample of the parameters, EMA weights and Adam first moment) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_kernel_timing and not args.full:
+        ap.error("--dump-kernel-timing is written by the roofline pass of a --full run")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args)), flush=True)
         return
@@ -640,7 +696,7 @@ def main():
 
     # ---- dominant-kernel roofline: instrumented pass, HIP events around every conv launch ----
     roofline = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         from joligen_amd import ops
 
         from joligen_amd.modules import unet_exec
@@ -713,10 +769,10 @@ def main():
             roofline["step_frac_of_mfma_peak"] = round(step_tflop / (ms_per_step * 1e-3) / PEAK_BF16_TFLOPS, 4)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_subprocess(args)
     cut, extra = None, {}
-    if rank == 0 and world == 1 and args.model == "palette" and not args.no_cut_leg and not args.force_exchange:
+    if args.full and rank == 0 and world == 1 and args.model == "palette" and not args.no_cut_leg and not args.force_exchange:
         # the CUT half of BASELINE's metric ("DDPM UNet & CUT G+D step") and configs[3] / configs[4] on the same line, each in its own
         # process and never at the palette line's expense
         # the palette numbers are taken: hand the parent's cached device memory back before the legs allocate theirs (the pool's boxes are shared --
@@ -748,13 +804,24 @@ def main():
                        "global_batch": args.batch * world, "per_gpu_batch": args.batch, "image_size": args.size,
                        "efficient": bool(args.efficient), "parallelism": f"dp{world}", "final_loss": round(loss, 6),
                        "n_ranks_seen": n_ranks_seen, **({"step_driver": model.step_driver, "step_driver_note": model.step_driver_note} if args.model == "cut" else {})},
-            "roofline": roofline, "cpu_baseline": cpu, "cut": cut,
+            **({"roofline": roofline, "cpu_baseline": cpu, "cut": cut, **extra} if args.full else {}),
         }
-        line.update(extra)
         if per_rank is not None:
             line["per_rank"] = per_rank
         if exch is not None:
             line["exchange"] = exch
+    if args.dump_outputs:
+        # not the timed model: its state after W + K steps carries this run's own summation order (DUMP_STEPS); every rank replays
+        # (a data-parallel model is built with collectives), rank 0 writes
+        import gc
+
+        model = None
+        gc.collect()
+        torch.cuda.empty_cache()
+        replay = replay_for_dump(args, rank, local_rank, world, batch)
+        if rank == 0:
+            dump_outputs(replay, args.dump_outputs)
+        replay = None
     # RCCL prints its banner through C stdio (block-buffered when stdout is a pipe, i.e. written at exit): every rank flushes it
     # now, so that rank 0's JSON line is the LAST line of the job's stdout
     import ctypes
@@ -763,7 +830,10 @@ def main():
     if dist.is_initialized():
         dist.barrier()
     if rank == 0:
-        emit(line)
+        if args.full:
+            emit(line)
+        else:
+            print(json.dumps(line), flush=True)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -26,10 +26,10 @@ tests)
   timeout 600 python -m pytest tests -v -m gpu -p no:cacheprovider > $O/${TAG}_gpu_pytest_full.log 2>&1
   tail -3 $O/${TAG}_gpu_pytest_full.log | tee -a $O/${TAG}_evidence.log ;;
 bench)
-  timeout 500 python bench.py 2> $O/${TAG}_bench.err | tail -1 > $O/${TAG}_bench_line.json
+  timeout 500 python bench.py --full 2> $O/${TAG}_bench.err | tail -1 > $O/${TAG}_bench_line.json
   cut -c1-600 $O/${TAG}_bench_line.json ;;
 prof)
-  timeout 120 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cut-leg --dump-kernel-timing $O/${TAG}_per_layer_kernel_timing.txt > /dev/null 2>&1
+  timeout 120 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cut-leg --dump-kernel-timing $O/${TAG}_per_layer_kernel_timing.txt > /dev/null 2>&1
   export JG_TRACE_MARK=1      # steady-state window for tools/rocpd_stats.py (4 timed steps)
   B="python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-cut-leg"
   cd /tmp
@@ -50,7 +50,7 @@ prof)
 cutprof)
   export JG_TRACE_MARK=1
   CB="python $R/bench.py --model cut --netG segformer_attn_conv --netDs projected_d,basic --proj vitsmall --batch 16 --steps 4 --warmup 5 --no-cpu-baseline --no-kernel-timing"
-  timeout 120 python bench.py --model cut --netG segformer_attn_conv --netDs projected_d,basic --proj vitsmall --batch 16 --steps 10 --warmup 3 --no-cpu-baseline --dump-kernel-timing $O/${TAG}_cut_per_layer_kernel_timing.txt > /dev/null 2>&1
+  timeout 120 python bench.py --full --model cut --netG segformer_attn_conv --netDs projected_d,basic --proj vitsmall --batch 16 --steps 10 --warmup 3 --no-cpu-baseline --dump-kernel-timing $O/${TAG}_cut_per_layer_kernel_timing.txt > /dev/null 2>&1
   cd /tmp
   timeout 150 rocprofv3 --kernel-trace -d $O/${TAG}_ckt -o kt -- $CB > $O/${TAG}_ckt.log 2>&1
   cd $R
@@ -78,7 +78,7 @@ lines)
     timeout 120 python bench.py --model cut --netG $1 --netDs $2 --batch 16 --steps 10 --warmup 3 --no-kernel-timing --no-cpu-baseline 2>/dev/null | tail -1 >> $O/${TAG}_cut_bench_lines.json
   done
   # BASELINE configs[3] (512x512, non-efficient, batch 8) and configs[4] (cm_model, batch 64)
-  timeout 120 python bench.py --size 512 --batch 8 --efficient 0 --steps 20 --no-cut-leg --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_c4_512_bench_line.json
-  timeout 120 python bench.py --model cm --batch 64 --steps 20 --no-cut-leg --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_cm_bench_line.json
+  timeout 120 python bench.py --full --size 512 --batch 8 --efficient 0 --steps 20 --no-cut-leg --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_c4_512_bench_line.json
+  timeout 120 python bench.py --full --model cm --batch 64 --steps 20 --no-cut-leg --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_cm_bench_line.json
   cut -c1-200 $O/${TAG}_cut_bench_lines.json $O/${TAG}_c4_512_bench_line.json $O/${TAG}_cm_bench_line.json ;;
 esac
