@@ -229,8 +229,7 @@ class BaseModel:
             if len(self.opt.gpu_ids) > 1 and self.niter % self.opt.train_iter_size != 0:
                 stack.enter_context(parallel.no_sync())
             for group in self.networks_groups:
-                for network in self.model_names:
-                    self.set_requires_grad(getattr(self, "net" + network), network in group.networks_to_optimize, _frozen_structure=True)
+                self._group_flags(group)
                 for forward in group.forward_functions or []:
                     getattr(self, forward)()
                 for backward in group.backward_functions:
@@ -238,17 +237,26 @@ class BaseModel:
                 for loss in group.loss_backward:
                     ll = getattr(self, loss) / self.opt.train_iter_size
                     ll.backward()
-                loss_names = []
-                for temp in group.loss_names_list:
-                    loss_names += getattr(self, temp)
-                self.compute_step(group.optimizer, loss_names, group)
-                if self.opt.train_G_ema:
-                    for network in self.model_names:
-                        if network in group.networks_to_ema:
-                            self.ema_step(network)
+                self._group_finish(group)
             for obj in self.objects_to_update:
                 obj.update(self.niter)
         self.poll_overflow()
+
+    def _group_flags(self, group):
+        """only the group's networks take gradients"""
+        for network in self.model_names:
+            self.set_requires_grad(getattr(self, "net" + network), network in group.networks_to_optimize, _frozen_structure=True)
+
+    def _group_finish(self, group):
+        """the group's optimizer step(s) and EMA updates"""
+        loss_names = []
+        for temp in group.loss_names_list:
+            loss_names += getattr(self, temp)
+        self.compute_step(group.optimizer, loss_names, group)
+        if self.opt.train_G_ema:
+            for network in self.model_names:
+                if network in group.networks_to_ema:
+                    self.ema_step(network)
 
     def compute_step(self, optimizers_names, loss_names, group=None):
         """:1250-1282.  The EMA update of the group's networks is fused into the optimizer launch

@@ -73,7 +73,7 @@ class PatchSampleF(nn.Module):
                 patch_id = patch_ids[feat_id].reshape(-1)
             else:
                 # `torch.randperm(H * W)[:P]` of the reference (cut_networks.py:57-60) as P distinct uniform positions from ONE Philox draw
-                # + top-k: the same distribution, no host synchronisation, and capturable in a hipGraph (cut_model._g_capture) with the
+                # + top-k: the same distribution, no host synchronisation, and capturable in a hipGraph (cut_step.CUTStepDriver._g_capture) with the
                 # SAME numbers as the eager launch sequence draws from the same generator state
                 P = int(min(num_patches, H * W))
                 patch_id = torch.rand(H * W, device=feat.device).topk(P).indices

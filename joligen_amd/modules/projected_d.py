@@ -470,7 +470,7 @@ class _FrozenBN(nn.Module):
                 sh = self.bias.detach().float() - self.running_mean.float() * sc
                 if self._affine is None or self._affine[0].shape != sc.shape or self._affine[0].device != sc.device:
                     self._affine = (sc.contiguous(), sh.contiguous())
-                else:       # refreshed IN PLACE: a captured hipGraph (cut_model._d_half_from_graph) holds these addresses
+                else:       # refreshed IN PLACE: a captured hipGraph (cut_step.CUTStepDriver.d_from_graph) holds these addresses
                     self._affine[0].copy_(sc)
                     self._affine[1].copy_(sh)
             self._key = key

@@ -416,3 +416,141 @@ def test_hip_graphs_safe_flag():
     assert run(None) == ["True", "0"]
     assert run("0") == ["True", "0"]
     assert run("1") == ["False", "1"]
+
+
+def test_cut_gate_truth_table(monkeypatch):
+    """models/cut_step.gate: an option under its environment variable, read at call time.  `=0` always switches off; `=1` forces the path on
+    over a false option only for the tri-state gates (JG_FORK_GAN / JG_GRAPH_G / JG_GRAPH_D), not for the switch-off-only ones."""
+    from types import SimpleNamespace
+
+    from joligen_amd.models.cut_step import gate
+
+    absent = object()
+    for force in (False, True):
+        for option in (True, False, absent):
+            for default in (True, False):
+                for env in (None, "0", "1"):
+                    opt = SimpleNamespace() if option is absent else SimpleNamespace(jg_x=option)
+                    monkeypatch.delenv("JG_X", raising=False) if env is None else monkeypatch.setenv("JG_X", env)
+                    value = default if option is absent else option
+                    want = env != "0" and (value or (force and env == "1"))
+                    got = gate(opt, "jg_x", "JG_X", default, force=force)
+                    assert got is want, (force, option, default, env, got)
+    monkeypatch.delenv("JG_X", raising=False)
+    assert gate(SimpleNamespace(), "jg_x", "JG_X") is True          # an absent option defaults to on
+
+
+def test_cut_captured_half_bookkeeping(monkeypatch):
+    """models/cut_step.CapturedHalf with a fake capture function and no GPU: at most three captured states, a failure is sticky (the capture
+    function is never called again) and leaves the warning and the note the tests and bench.py grep for, and the snapshot is written back
+    without a version bump (the frozen-BN tables key on tensor versions)."""
+    import warnings
+    from types import SimpleNamespace
+
+    import joligen_amd
+    from joligen_amd.models.cut_step import CapturedHalf
+
+    monkeypatch.setattr(joligen_amd, "HIP_GRAPHS_SAFE", True)
+    for v in ("JG_GRAPH_G", "JG_GRAPH_D", "JG_DBG_GRAPH_CANARY_FAIL"):
+        monkeypatch.delenv(v, raising=False)
+
+    def fake_model():
+        return SimpleNamespace(opt=SimpleNamespace(), act_dtype=torch.bfloat16, niter=3, step_driver_note="", device=torch.device("cpu"))
+
+    def fake_net():
+        buf = torch.arange(4.0)
+        return SimpleNamespace(arena=SimpleNamespace(g=torch.ones(8), p=torch.zeros(8)), training=True, buffers=lambda: [buf], buf=buf)
+
+    def halves(m):
+        return (CapturedHalf(m, "jg_graph_G", "JG_GRAPH_G", "generator", "generator graph dropped", "G"),
+                CapturedHalf(m, "jg_graph_D", "JG_GRAPH_D", "discriminator", "graph dropped", "1", "HIP_GRAPHS_SAFE is False (test)"))
+
+    # the gate and the shared guards
+    m = fake_model()
+    g, d = halves(m)
+    assert g.ready() and d.ready()
+    m.niter = 2
+    assert not g.ready()
+    m.niter, m.act_dtype = 3, torch.float16
+    assert not d.ready()
+    m.act_dtype = torch.bfloat16
+    monkeypatch.setenv("JG_GRAPH_D", "0")
+    assert g.ready() and not d.ready()
+    monkeypatch.delenv("JG_GRAPH_D")
+    m.opt.jg_graph_G = False
+    assert not g.ready()
+    monkeypatch.setenv("JG_GRAPH_G", "1")
+    assert g.ready()
+    monkeypatch.setattr(joligen_amd, "HIP_GRAPHS_SAFE", False)
+    assert not g.ready() and m.step_driver_note == ""              # only the discriminator half says why
+    assert not d.ready() and "HIP_GRAPHS_SAFE" in m.step_driver_note
+    monkeypatch.setattr(joligen_amd, "HIP_GRAPHS_SAFE", True)
+
+    # a passing capture: cached per key, three keys at most, touched state restored without a version bump
+    m = fake_model()
+    g, d = halves(m)
+    net, calls = fake_net(), []
+    versions = (net.arena.g._version, net.buf._version)
+
+    def capture(restore):
+        calls.append(restore)
+        net.arena.g.data.mul_(3.0)                                 # what two replays of a canary do to the state
+        net.buf.data.add_(1.0)
+        d.check(torch.tensor(2.0), torch.tensor(2.0 + 1e-4), 1e-3, "an untouched graph")
+        d.check(torch.tensor([2.0, 5.0]), torch.tensor([2.001, 5.1]), torch.tensor([5e-3, 5e-2]), "the generator graphs")
+        return "state%d" % len(calls)
+
+    assert d.get(("a",), [net], capture) == "state1" and d.get(("a",), [net], capture) == "state1" and len(calls) == 1
+    assert torch.equal(net.arena.g, torch.ones(8)) and torch.equal(net.buf, torch.arange(4.0))
+    assert (net.arena.g._version, net.buf._version) == versions
+    net.arena.g.data.fill_(7.0)
+    calls[0]()                                                     # the restore handed to the capture function, on its own
+    assert torch.equal(net.arena.g, torch.ones(8)) and net.arena.g._version == versions[0]
+    assert d.get(("b",), [net], capture) == "state2" and d.get(("c",), [net], capture) == "state3"
+    assert d.get(("d",), [net], capture) is None and len(calls) == 3 and len(d.cache) == 3       # a fourth distinct key is refused ...
+    assert not d.failed and m.step_driver_note == "" and d.get(("b",), [net], capture) == "state2"   # ... and is no failure
+    net.training = False                                           # the networks' mode and arena address are part of the key
+    assert d.get(("a",), [net], capture) is None and len(calls) == 3
+
+    # the canary's comparison: relative tolerance, non-finite values, the forced failure of the tests
+    for first, second, tol in ((torch.tensor(2.0), torch.tensor(2.01), 1e-3), (torch.tensor(2.0), torch.tensor(float("nan")), 1e-3),
+                               (torch.tensor([2.0, 5.0]), torch.tensor([2.0, 5.5]), torch.tensor([5e-3, 5e-2]))):
+        with pytest.raises(RuntimeError, match="disagree after interleaved eager launches"):
+            d.check(first, second, tol, "an untouched graph")
+    monkeypatch.setenv("JG_DBG_GRAPH_CANARY_FAIL", "G")
+    d.check(torch.tensor(2.0), torch.tensor(2.0), 1e-3, "an untouched graph")          # "G" targets the generator half only
+    with pytest.raises(RuntimeError):
+        g.check(torch.tensor(2.0), torch.tensor(2.0), 1e-3, "the generator graphs")
+    monkeypatch.setenv("JG_DBG_GRAPH_CANARY_FAIL", "1")
+    g.check(torch.tensor(2.0), torch.tensor(2.0), 1e-3, "the generator graphs")
+    with pytest.raises(RuntimeError):
+        d.check(torch.tensor(2.0), torch.tensor(2.0), 1e-3, "an untouched graph")
+
+    # failing captures: warning, note, sticky flag, state restored; both halves append to the note
+    m = fake_model()
+    g, d = halves(m)
+    net, calls = fake_net(), []
+
+    def failing(half):
+        def capture(restore):
+            calls.append(half.option)
+            net.arena.g.data.mul_(3.0)
+            half.check(torch.tensor(2.0), torch.tensor(2.0), 1e-3, "an untouched graph")          # JG_DBG_GRAPH_CANARY_FAIL=1 / G
+            return "state"
+        return capture
+
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter("always")
+        assert d.get(("a",), [net], failing(d)) is None
+        monkeypatch.setenv("JG_DBG_GRAPH_CANARY_FAIL", "G")
+        assert g.get(("a",), [net], failing(g)) is None
+        monkeypatch.delenv("JG_DBG_GRAPH_CANARY_FAIL")
+        for _ in range(3):                                         # sticky: the capture function is never called again
+            assert d.get(("a",), [net], failing(d)) is None and g.get(("b",), [net], failing(g)) is None
+            assert not d.ready() and not g.ready()
+    assert calls == ["jg_graph_D", "jg_graph_G"] and d.failed and g.failed and not d.cache and not g.cache
+    texts = [str(w.message) for w in rec]
+    assert len(texts) == 2 and texts[0].startswith("jg_graph_D: the discriminator half stays eager")
+    assert texts[1].startswith("jg_graph_G: the generator half stays eager")
+    assert m.step_driver_note.startswith("graph dropped: ") and "; generator graph dropped: " in m.step_driver_note
+    assert torch.equal(net.arena.g, torch.ones(8)) and net.arena.g._version == versions[0]

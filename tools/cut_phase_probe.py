@@ -36,9 +36,9 @@ for _ in range(8):
     step()
 torch.cuda.synchronize()
 print("driver", model.step_driver, model.step_driver_note)
-gst = next(iter(model._gg_graphs.values()))
-dst = next(iter(model._dg_graphs.values()))
-side = model._d_stream
+gst = next(iter(model.driver.g_half.cache.values()))
+dst = next(iter(model.driver.d_half.cache.values()))
+side = model.driver.d_stream
 
 
 def timeit(fn, n=a.n):
@@ -55,20 +55,20 @@ def timeit(fn, n=a.n):
 def d_on_side():
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        dst["graph"].replay()
+        dst.graph.replay()
     torch.cuda.current_stream().wait_stream(side)
 
 
 def fb():
-    gst["fwd"].replay()
-    gst["bwd"].replay()
+    gst.fwd.replay()
+    gst.bwd.replay()
 
 
 def b_and_d():
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        dst["graph"].replay()
-    gst["bwd"].replay()
+        dst.graph.replay()
+    gst.bwd.replay()
     torch.cuda.current_stream().wait_stream(side)
 
 
@@ -78,8 +78,8 @@ def opt_only():
 
 
 res = dict(
-    graph_F=timeit(lambda: gst["fwd"].replay()),
-    graph_B=timeit(lambda: gst["bwd"].replay()),
+    graph_F=timeit(lambda: gst.fwd.replay()),
+    graph_B=timeit(lambda: gst.bwd.replay()),
     graph_D=timeit(d_on_side),
     F_then_B=timeit(fb),
     B_with_D=timeit(b_and_d),

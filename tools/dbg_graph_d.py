@@ -62,19 +62,19 @@ def make(graph):
 
 def poke(m):
     """replay the captured, untouched graph after each eager activity: every line should print the same loss"""
-    st, dn = m._dg, m.discriminators_names[0]
+    st, dn = next(iter(m.driver.d_half.cache.values())), m.discriminators_names[0]
 
     def replay(tag):
-        st["graph"].replay()
+        st.graph.replay()
         torch.cuda.synchronize()
-        print("   ", tag, [float(v) for v in st["vals"]])
+        print("   ", tag, [float(v) for v in st.vals])
 
     replay("replay")
     with torch.no_grad():
-        m._net(dn)(st["real"])
+        m._net(dn)(st.real)
     torch.cuda.synchronize()
     replay("after an eager no-grad D forward on the default stream")
-    y = m._net(dn)(st["real"])
+    y = m._net(dn)(st.real)
     torch.cuda.synchronize()
     replay("after an eager D forward with autograd")
     y.float().sum().backward()
@@ -121,14 +121,14 @@ def main():
                 a = m._net(dn).arena
                 row.append("%s: |g| %.4e |p| %.6e" % (dn, float(a.g.norm()), float(a.p.norm())))
             print(i, " | ".join(row))
-            st = getattr(m, "_dg", None) if graph else None
+            st = next(iter(m.driver.d_half.cache.values()), None) if graph else None
             if st is None:
                 continue
             if i == 3 and os.environ.get("DBG_REPLAY"):
                 for r in range(3):
-                    st["graph"].replay()
+                    st.graph.replay()
                     torch.cuda.synchronize()
-                    print("   extra replay", r, float(st["tot"]), [float(v) for v in st["vals"]])
+                    print("   extra replay", r, float(st.tot), [float(v) for v in st.vals])
             if i == ITS + 1 and os.environ.get("DBG_GRADS"):
                 for dn in m.discriminators_names:
                     for name, prm in m._net(dn).named_parameters():
@@ -137,8 +137,8 @@ def main():
                 c = getattr(m, m.discriminators_names[0] + "_loss_calculator")
                 a = m._net(m.discriminators_names[0]).arena
                 print("    real %.5e fake %.5e pred_real %.5e w16 %.6e w16T %.6e vals %s" % (
-                    float(st["real"].float().norm()), float(st["fakes"][0].float().norm()), float(c.pred_real.float().norm()),
-                    float(a.w16.float().norm()), float(a.w16T.float().norm()), [float(v) for v in st["vals"]]))
+                    float(st.real.float().norm()), float(st.fakes[0].float().norm()), float(c.pred_real.float().norm()),
+                    float(a.w16.float().norm()), float(a.w16T.float().norm()), [float(v) for v in st.vals]))
             if i == 3 and os.environ.get("DBG_POKE"):
                 poke(m)
 
