@@ -610,6 +610,22 @@ int jg_resample_u8(const uint8_t* in, uint8_t* out, const int32_t* bounds, const
 int jg_resize_nearest_u8(const uint8_t* in, uint8_t* out, const int32_t* ytab, const int32_t* xtab, int B, int Hin, int Win, int Hout, int Wout,
                          jg_stream_t s);
 
+/* Conditioning image of the palette model's super_resolution task (models/palette_model.py:120-130 transform_lr / transform_hr,
+ * :546-548 cond_image_creation "low_res"): y = Resize((H, W))(Resize((Hlo, Wlo))(x)), torchvision Resize on a tensor =
+ * F.interpolate(bilinear, antialias=True, align_corners=False).  x, y: fp32 NCHW planes [planes][H][W] (planes = B * C), x != y.  ONE
+ * launch: the low-resolution image stays in LDS.  The caller supplies the tap tables of the four 1-D passes (down along H, down along W,
+ * up along H, up along W), per pass: first source index int32 [n_out], tap count int32 [n_out], normalised fp32 taps [n_out][K] --
+ * K = Kdown for both down passes (the wider axis' 2 ceil(n_in / n_out) + 1; rows of the narrower one zero-padded), K = 3 for the up
+ * passes -- computed as ATen computes them (joligen_amd/resize_aa.py).  No atomics: bit-identical from run to run.
+ * JG_ERR_UNSUPPORTED: Kdown above 65 taps, or no band of output rows whose input rows fit the 160 KiB of LDS (every ratio in [1, 8] up
+ * to 512 x 512 fits).  jg_lowres_roundtrip_band: the rows of output one workgroup produces for that shape (> 0), or the same error
+ * codes -- the support probe, no launch. */
+int jg_lowres_roundtrip_f32(const float* x, float* y, const int32_t* dh_min, const int32_t* dh_size, const float* dh_w, const int32_t* dw_min,
+                            const int32_t* dw_size, const float* dw_w, const int32_t* uh_min, const int32_t* uh_size, const float* uh_w,
+                            const int32_t* uw_min, const int32_t* uw_size, const float* uw_w, int planes, int H, int W, int Hlo, int Wlo,
+                            int Kdown, jg_stream_t s);
+int jg_lowres_roundtrip_band(int H, int W, int Hlo, int Wlo, int Kdown);
+
 /* NHWC(T, Cpad) <-> NCHW(fp32, C) layout converters at the module boundary. */
 int jg_nhwc_to_nchw_f32(int dtype, const void* x, float* y, int B, int C, int H, int W, int Cpad, jg_stream_t s);
 int jg_nchw_f32_to_nhwc(int dtype, const float* x, void* y, int B, int C, int H, int W, int Cpad, jg_stream_t s);

@@ -1,5 +1,5 @@
 """palette_model (DDPM) training step on MI355X: mirror of /root/reference/models/palette_model.py
-(`__init__` :116-285, `set_input` :287-366 (inpainting / pix2pix, cond_image_creation="y_t"),
+(`__init__` :116-285, `set_input` :287-366, 546-548 (inpainting / pix2pix with cond_image_creation="y_t", super_resolution with "low_res"),
 `compute_palette_loss` :558-620) and models/diffusion_networks.py `define_G` (:24-139,361-376)
 for `G_netG="unet_mha"`.
 
@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from .. import ops
+from .. import ops, resize_aa
 from ..modules.diffusion_generator import DiffusionGenerator, PaletteDenoiseFn
 from ..modules.unet_generator_attn import UNet
 from .base_model import BaseModel, NetworkGroup
@@ -53,9 +53,19 @@ class PaletteModel(BaseModel):
     def __init__(self, opt, rank):
         super().__init__(opt, rank)
         self.task = opt.alg_diffusion_task
-        if self.task not in ("inpainting", "pix2pix"):
+        if self.task not in ("inpainting", "pix2pix", "super_resolution"):
             raise NotImplementedError(f"alg_diffusion_task={self.task!r} is outside the SURVEY.md 8 hot path")
-        if opt.alg_diffusion_cond_image_creation != "y_t":
+        if self.task == "super_resolution":
+            # palette_model.py:120-130: the conditioning image is the ground truth resized to S_lo and back (one kernel, ops.lowres_roundtrip)
+            opt.alg_diffusion_cond_image_creation = "low_res"
+            scale, S = opt.alg_diffusion_super_resolution_scale, opt.data_crop_size
+            if not scale >= 1:
+                raise ValueError(f"alg_diffusion_super_resolution_scale={scale!r}: the low-resolution image cannot be larger than the crop")
+            self.data_crop_size_low_res = resize_aa.low_size(S, scale)
+            if self.data_crop_size_low_res < 1:
+                raise ValueError(f"alg_diffusion_super_resolution_scale={scale!r} leaves no pixel of a {S}-pixel crop")
+            resize_aa.band_rows(S, S, self.data_crop_size_low_res, self.data_crop_size_low_res)    # NotImplementedError here, not mid-step
+        elif opt.alg_diffusion_cond_image_creation != "y_t":
             raise NotImplementedError("only alg_diffusion_cond_image_creation='y_t' is implemented")
         if opt.alg_palette_loss not in ("MSE", "L1", "multiscale_MSE", "multiscale_L1"):
             raise NotImplementedError(f"alg_palette_loss={opt.alg_palette_loss!r}")
@@ -108,7 +118,11 @@ class PaletteModel(BaseModel):
         a = data["A"].to(self.device, non_blocking=True)
         if a.dim() != 4:
             raise NotImplementedError("temporal (5-D) batches are outside the SURVEY.md 8 hot path")
-        if self.task == "inpainting":
+        if self.task == "super_resolution":     # :364-366: only A is read; :546-548: the low-resolution round trip of it conditions the UNet
+            self.gt_image = a
+            self.mask = None
+            self.y_t = ops.lowres_roundtrip(a.float(), (self.data_crop_size_low_res,) * 2)
+        elif self.task == "inpainting":
             self.y_t = a
             self.gt_image = data["B"].to(self.device, non_blocking=True)
             self.mask = data["B_label_mask"].to(self.device, non_blocking=True)
@@ -149,7 +163,7 @@ class PaletteModel(BaseModel):
             setattr(self, "loss_G_" + res, val / lam if lam not in (0, 1) else val)
         self.loss_G_tot = loss
 
-    # palette_model.py:622-887 (inpainting / pix2pix; no per-class, reference-image or video branches)
+    # palette_model.py:622-887 (inpainting / pix2pix and super_resolution, which samples as pix2pix does, :838-844; no per-class, reference-image or video branches)
     @torch.no_grad()
     def inference(self, nb_imgs, offset=0):
         netG = self._net("G_A")
@@ -159,8 +173,8 @@ class PaletteModel(BaseModel):
                                                          mask=self.mask[:nb_imgs], sample_num=self.sample_num, cls=cls,
                                                          ddim_num_steps=self.ddim_num_steps, ddim_eta=self.ddim_eta, noises=self.sampling_noises)
         else:
-            self.output, self.visuals = netG.restoration(y_cond=self.cond_image[:nb_imgs], sample_num=self.sample_num, cls=cls,
-                                                         noises=self.sampling_noises)
+            self.output, self.visuals = netG.restoration(y_cond=self.cond_image[:nb_imgs], sample_num=self.sample_num,
+                                                         cls=None if self.task == "super_resolution" else cls, noises=self.sampling_noises)
         self.fake_B = self.output
         self._publish_visuals(nb_imgs, offset)
 

@@ -1406,6 +1406,43 @@ def ddpm_prepare(y0, ycond, noise, mask, gammas, act_dtype, cpad=8):
     return xin
 
 
+def lowres_roundtrip(x, scale_or_size, out=None):
+    """Resize((H, W))(Resize((Hlo, Wlo))(x)) with torchvision's anti-aliased bilinear Resize, in one launch (jg_lowres_roundtrip_f32): the
+    conditioning image of the palette model's super_resolution task (palette_model.py:120-130, 546-548).  x: fp32 NCHW; `scale_or_size`: a
+    number = the down-scaling factor (Hlo = int(H / scale), as the reference sizes it) or a pair (Hlo, Wlo); `out`: optional contiguous fp32
+    tensor of x's shape to write into (ctypes path only).  Not differentiated: x is data."""
+    from . import resize_aa
+
+    B, Cc, H, W = x.shape
+    if isinstance(scale_or_size, (tuple, list)):
+        Hlo, Wlo = (int(v) for v in scale_or_size)
+    else:
+        Hlo, Wlo = resize_aa.low_size(H, scale_or_size), resize_aa.low_size(W, scale_or_size)
+    if not (1 <= Hlo <= H and 1 <= Wlo <= W):
+        raise ValueError(f"lowres_roundtrip: low-resolution size {Hlo}x{Wlo} outside 1..{H} x 1..{W}")
+    if TORCH_OPS_BOUNDARY and not _IN_OP and out is None:
+        return torch.ops.jg355.lowres_roundtrip(x, Hlo, Wlo)
+    _require_cuda(x, out)
+    if x.dtype != torch.float32:
+        raise TypeError(f"lowres_roundtrip takes the fp32 ground-truth image, got {x.dtype}")
+    resize_aa.band_rows(H, W, Hlo, Wlo)          # NotImplementedError for a shape the kernel does not take
+    x = x.contiguous()
+    if out is None:
+        y = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("lowres_roundtrip: `out` must be a contiguous fp32 tensor of x's shape on x's device")
+    else:
+        y = out
+    if x.numel() == 0:
+        return y
+    kd = max(resize_aa.aa_taps(H, Hlo), resize_aa.aa_taps(W, Wlo))
+    args = []
+    for n_in, n_out, k in ((H, Hlo, kd), (W, Wlo, kd), (Hlo, H, 3), (Wlo, W, 3)):
+        args += [t.data_ptr() for t in resize_aa.device_tables(n_in, n_out, x.device, k)]
+    check(_lib.lib().jg_lowres_roundtrip_f32(x.data_ptr(), y.data_ptr(), *args, B * Cc, H, W, Hlo, Wlo, kd, _st()), "jg_lowres_roundtrip_f32")
+    return y
+
+
 class _MSELossFn(JGFunction):
     @staticmethod
     def forward(ctx, nh, noise, mask, w, lam, grad_scale, Cc):
@@ -1910,6 +1947,22 @@ def _op_ddpm_prepare(y0: torch.Tensor, ycond: torch.Tensor, noise: torch.Tensor,
 def _(y0, ycond, noise, mask, gammas, fp16, cpad):
     B, _, H, W = y0.shape
     return y0.new_empty((B, H, W, cpad), dtype=torch.float16 if fp16 else torch.bfloat16)
+
+
+@torch.library.custom_op("jg355::lowres_roundtrip", mutates_args=())
+def _op_lowres_roundtrip(x: torch.Tensor, hlo: int, wlo: int) -> torch.Tensor:
+    """anti-aliased bilinear resize to (hlo, wlo) and back (palette_model.py:546-548); not differentiated (the ground truth is data)"""
+    global _IN_OP
+    prev, _IN_OP = _IN_OP, True
+    try:
+        return lowres_roundtrip(x, (hlo, wlo))
+    finally:
+        _IN_OP = prev
+
+
+@_op_lowres_roundtrip.register_fake
+def _(x, hlo, wlo):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op("jg355::ddpm_mse_loss", mutates_args=())
