@@ -435,6 +435,17 @@ int jg_nce_sinkhorn_fwd(const float* S, float* K, float* u_hist, float* v_hist, 
                         jg_stream_t s);
 int jg_nce_ce(const float* S, const float* u, int64_t ustride, const float* v, int64_t vstride, float* loss_rows, float* dS,
               float* gW, int nimg, int P, float T, float pm1, const float* grow, float* gpos, float eps, jg_stream_t s);
+/* SRC_hDCE (models/modules/NCE/SRC.py:46-75, hDCE.py:16-38) on RAW Gram matrices S[nimg][P][P] = q k^T and G[nimg][P][P] = k k^T:
+ * rinv_j = 1 / (sqrt(G_jj) + 1e-7), Gh_ij = G_ij rinv_i rinv_j, m_i = max_{j != i} Gh_ij, w_ij = exp((Gh_ij - m_i) / gamma) (never
+ * stored), a_ij = S_ij w_ij / T with a_ii = -10 / T, A_i = logsumexp_j a_ij, pos_i = S_ii / T.
+ *   dS == NULL : forward.  loss_rows_i = log(e^A_i + e^pos_i) - pos_i; stats[3][nimg * P] = m | A | rinv for the backward; W (may be
+ *                NULL) receives the weights [nimg][P][P] with a zero diagonal (1 off the diagonal of an unweighted problem).
+ *   dS != NULL : backward of A_i - pos_i in one pass from stats: dS_ij = grow_i e^(a_ij - A_i) w_ij / T (diagonal 0),
+ *                gpos_i = -grow_i / T (the positive logit sees k detached).  loss_rows and W are not used (W must be NULL).
+ * Problem b is weighted iff (b % wperiod) < wcount; the others run with w == 1 and never read G (G may be NULL with wcount == 0).
+ * No atomics, no allocation, no synchronisation: capturable, bit-reproducible.  Any P >= 1. */
+int jg_nce_hdce(const float* S, const float* G, float* stats, float* loss_rows, float* dS, float* gpos, const float* grow, float* W,
+                int nimg, int P, float T, float gamma, int wperiod, int wcount, jg_stream_t s);
 int jg_nce_sinkhorn_bwd(const float* K, const float* u_hist, const float* v_hist, float* gW, float* ds_hist, float* dr_hist,
                         float* dS, int nimg, int P, int niter, jg_stream_t s);
 

@@ -133,6 +133,7 @@ SIGNATURES = {
     "jg_row_axpy": [c_p, c_p, c_p, c_i64, c_i32, c_p],
     "jg_nce_sinkhorn_fwd": [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_p],
     "jg_nce_ce": [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i32, c_i32, c_f32, c_f32, c_p, c_p, c_f32, c_p],
+    "jg_nce_hdce": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_f32, c_f32, c_i32, c_i32, c_p],
     "jg_nce_sinkhorn_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p],
     "jg_layernorm_fwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_f32, c_p],
     "jg_vit_attention_fwd": [c_i32, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],

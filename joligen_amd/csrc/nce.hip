@@ -3,9 +3,10 @@
 //                          the small nn.Linear layers of the embedding path) -- LDS-tiled 64x64x32 on v_mfma_f32_32x32x2_f32
 //   * jg_nce_sinkhorn_fwd  MoNCE optimal-transport weights: K = exp(S), 50 Sinkhorn iterations, one workgroup per image
 //   * jg_nce_ce            cross-entropy over [l_pos | l_neg] / T per patch, loss + dS (+ dW for MoNCE) in one pass
+//   * jg_nce_hdce          SRC_hDCE: weights from the key Gram matrix, weighted logsumexp loss and its dS, fused (weights never stored)
 //   * jg_nce_sinkhorn_bwd  reverse sweep through the Sinkhorn iterations (the reference differentiates through them w.r.t. q)
 //   * jg_nce_sinkhorn_gk   dS += K .* (rank-2T update assembled from the forward/backward histories)
-// reference: models/modules/NCE/base_NCE.py:17-77, monce.py:16-33, sinkhorn.py:6-58
+// reference: models/modules/NCE/base_NCE.py:17-77, monce.py:16-33, sinkhorn.py:6-58, SRC.py:46-75, hDCE.py:16-38
 #include <stdlib.h>
 
 #include "common.h"
@@ -708,6 +709,106 @@ __global__ __launch_bounds__(256) void nce_ce_kernel(const float* __restrict__ S
   }
 }
 
+// ---- hDCE: hard-negative-weighted contrastive loss (NCE/SRC.py:46-75 weights, NCE/hDCE.py:16-38 loss) ---------------------------
+// wave per patch row, like nce_ce_kernel.  S = q k^T and G = k k^T are RAW Gram matrices; the weights never reach memory:
+//   rinv_j = 1 / (sqrt(G_jj) + 1e-7), Gh_ij = G_ij rinv_i rinv_j, m_i = max_{j != i} Gh_ij, w_ij = exp((Gh_ij - m_i) / gamma)
+//   a_ij = S_ij w_ij / T (j != i), a_ii = -10 / T, A_i = logsumexp_j a_ij, pos_i = S_ii / T
+//   loss_i = log(e^A_i + e^pos_i) - pos_i;  the GRADIENT is that of A_i - pos_i (hDCE.py:24-36), weights detached
+// Problem b is weighted iff (b % wperiod) < wcount (integers: no mask array to upload inside a graph capture); an unweighted
+// problem runs with w == 1 and never reads G.  stats [3][rows] = m | A | rinv, written by the forward for the backward.
+// NV > 0: P <= 64 NV, the logits of the row are held in registers (one read of the S and G rows); NV == 0: any P, rows re-read.
+template <int NV>
+__global__ __launch_bounds__(256) void hdce_fwd_kernel(const float* __restrict__ S, const float* __restrict__ G, float* __restrict__ stats,
+                                                       float* __restrict__ loss_rows, float* __restrict__ W, long rows, int P, float invT,
+                                                       float invG, int wperiod, int wcount) {
+  const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const int i = row % P;
+  const long b = row / P;
+  const bool weighted = (b % wperiod) < wcount;
+  const float* Sr = S + row * P;
+  const float* Gr = weighted ? G + row * P : nullptr;
+  const float* Gd = weighted ? G + b * P * P : nullptr;      // Gd[j (P + 1)]: the diagonal, the only strided read
+  const float diag = -10.0f * invT;
+  const int nch = NV ? NV : (P + 63) / 64;
+  float rinv_i = 0.f, m = 0.f;
+  float gv[NV ? NV : 1], av[NV ? NV : 1];
+  if (weighted) {
+    rinv_i = 1.0f / (sqrtf(Gd[(long)i * (P + 1)]) + 1e-7f);
+    float mm = -INFINITY;
+    for (int c = 0; c < nch; ++c) {
+      const int j = lane + 64 * c;
+      if (j >= P) break;
+      const float gh = Gr[j] * rinv_i * (1.0f / (sqrtf(Gd[(long)j * (P + 1)]) + 1e-7f));
+      if (NV) gv[NV ? c : 0] = gh;
+      if (j != i) mm = fmaxf(mm, gh);
+    }
+    mm = wave_max(mm);
+    m = P > 1 ? mm : 0.f;      // P == 1: no negatives, no weight is ever used
+  }
+  // logit j of this row (j < P); W (tests / inspection) gets the weight, 0 on the diagonal
+  auto logit = [&](int c, int j, bool emit) -> float {
+    float w = 1.0f;
+    if (j != i && weighted) {
+      const float gh = NV ? gv[NV ? c : 0] : Gr[j] * rinv_i * (1.0f / (sqrtf(Gd[(long)j * (P + 1)]) + 1e-7f));
+      w = expf((gh - m) * invG);
+    }
+    if (emit && W) W[row * P + j] = j == i ? 0.f : w;
+    return j == i ? diag : Sr[j] * w * invT;
+  };
+  float mx = diag;      // the diagonal is one of the logits: a valid start for every lane
+  for (int c = 0; c < nch; ++c) {
+    const int j = lane + 64 * c;
+    if (j >= P) break;
+    const float a = logit(c, j, true);
+    if (NV) av[NV ? c : 0] = a;
+    mx = fmaxf(mx, a);
+  }
+  mx = wave_max(mx);
+  float se = 0.f;
+  for (int c = 0; c < nch; ++c) {
+    const int j = lane + 64 * c;
+    if (j >= P) break;
+    se += expf((NV ? av[NV ? c : 0] : logit(c, j, false)) - mx);
+  }
+  se = wave_sum(se);
+  if (lane == 0) {
+    const float A = mx + logf(se);
+    const float d = A - Sr[i] * invT;      // log(e^A + e^pos) - pos = softplus(A - pos): no cancellation where the loss is small
+    loss_rows[row] = fmaxf(d, 0.f) + log1pf(expf(-fabsf(d)));
+    stats[row] = m;
+    stats[rows + row] = A;
+    stats[2 * rows + row] = rinv_i;
+  }
+}
+
+// one pass over the S and G rows with the saved m_i, A_i, rinv: dS_ij = grow_i e^(a_ij - A_i) w_ij / T (0 on the diagonal), gpos_i = -grow_i / T
+__global__ __launch_bounds__(256) void hdce_bwd_kernel(const float* __restrict__ S, const float* __restrict__ G, const float* __restrict__ stats,
+                                                       float* __restrict__ dS, float* __restrict__ gpos, const float* __restrict__ grow, long rows,
+                                                       int P, float invT, float invG, int wperiod, int wcount) {
+  const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const int i = row % P;
+  const long b = row / P;
+  const bool weighted = (b % wperiod) < wcount;
+  const float* Sr = S + row * P;
+  const float* Gr = weighted ? G + row * P : nullptr;
+  const float* rinv = stats + 2 * rows + b * P;
+  const float m = stats[row], A = stats[rows + row], rinv_i = stats[2 * rows + row];
+  const float gs = grow[row];
+  if (lane == 0) gpos[row] = -gs * invT;
+  for (int j = lane; j < P; j += 64) {
+    float d = 0.f;
+    if (j != i) {
+      const float w = weighted ? expf((Gr[j] * rinv_i * rinv[j] - m) * invG) : 1.0f;
+      d = gs * expf(Sr[j] * w * invT - A) * w * invT;
+    }
+    dS[row * P + j] = d;
+  }
+}
+
 // y[r][:] += g[r] * x[r][:]
 __global__ void row_axpy_kernel(float* __restrict__ y, const float* __restrict__ g, const float* __restrict__ x, long R, int D) {
   const long total = R * D;
@@ -769,6 +870,25 @@ extern "C" int jg_nce_ce(const float* S, const float* u, int64_t ustride, const 
     hipLaunchKernelGGL((nce_ce_kernel<false>), grid, dim3(256), 0, (hipStream_t)s, S, u, (long)ustride, v, (long)vstride, loss_rows, dS, gW, rows, P, T, pm1, grow, gpos,
                        eps);
   }
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+
+extern "C" int jg_nce_hdce(const float* S, const float* G, float* stats, float* loss_rows, float* dS, float* gpos, const float* grow, float* W,
+                           int nimg, int P, float T, float gamma, int wperiod, int wcount, jg_stream_t s) {
+  if (!S || !stats || nimg < 1 || P < 1 || !(T > 0.f) || !(gamma > 0.f) || wperiod < 1 || wcount < 0 || wcount > wperiod) return JG_ERR_BAD_ARG;
+  if (wcount > 0 && !G) return JG_ERR_BAD_ARG;
+  if (dS ? (!grow || !gpos || W) : !loss_rows) return JG_ERR_BAD_ARG;
+  const long rows = (long)nimg * P;
+  if ((rows + 3) / 4 > 0x7fffffffL) return JG_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  const float invT = 1.0f / T, invG = 1.0f / gamma;
+  if (dS)
+    hipLaunchKernelGGL(hdce_bwd_kernel, grid, dim3(256), 0, (hipStream_t)s, S, G, stats, dS, gpos, grow, rows, P, invT, invG, wperiod, wcount);
+  else if (P <= 256)
+    hipLaunchKernelGGL((hdce_fwd_kernel<4>), grid, dim3(256), 0, (hipStream_t)s, S, G, stats, loss_rows, W, rows, P, invT, invG, wperiod, wcount);
+  else
+    hipLaunchKernelGGL((hdce_fwd_kernel<0>), grid, dim3(256), 0, (hipStream_t)s, S, G, stats, loss_rows, W, rows, P, invT, invG, wperiod, wcount);
   JG_CHECK_LAUNCH();
   return JG_OK;
 }

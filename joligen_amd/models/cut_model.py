@@ -2,7 +2,7 @@
 (`__init__` :216-503, `data_dependent_initialize` :505-548, `forward_cut` :611-688, `compute_G_loss_cut` :708-837,
 `calculate_feats` :848-887, `calculate_NCE_loss` :889-909) and models/base_gan_model.py (`compute_D_loss(_generic)`
 :341-419, `compute_G_loss_GAN(_generic)` :421-503) for the default configuration: G_netG='resnet', D_netDs=['basic'],
-alg_cut_netF='mlp_sample', alg_cut_nce_loss in {'monce', 'patchnce'}, nce_idt, lsgan, no semantic / multimodal / context /
+alg_cut_netF='mlp_sample', alg_cut_nce_loss in {'monce', 'patchnce', 'SRC_hDCE'}, nce_idt, lsgan, no semantic / multimodal / context /
 temporal / augmentation branches.
 
 Per iteration (reference order): group G = {G_A, F}: fake = G(cat(real_A, real_B)); loss_G_tot = lambda_GAN * lsgan(D(fake_B), 1)
@@ -11,10 +11,13 @@ image pool, loss_D_tot = (lsgan(D(real_B), 1) + lsgan(D(fake), 0)) / 2; backward
 Images are converted ONCE to NHWC 16-bit (3 -> 8 channels); every conv / norm / loss runs on the HIP kernels."""
 from __future__ import annotations
 
+import warnings
+
 import torch
 
 from .._autograd import JGFunction
 from .. import ops
+from ..modules.NCE.hdce import PatchHDCELoss
 from ..modules.NCE.patchnce import MoNCELoss, PatchNCELoss
 from ..modules.cut_networks import PatchSampleF
 from ..modules.discriminators import NLayerDiscriminator
@@ -27,7 +30,7 @@ from .cut_step import CUTStepDriver, gate
 CUT_DEFAULTS = dict(
     alg_cut_lambda_NCE=1.0, alg_cut_lambda_SRC=0.0, alg_cut_nce_idt=True, alg_cut_nce_layers="0,4,8,12,16",
     alg_cut_nce_includes_all_negatives_from_minibatch=False, alg_cut_nce_loss="monce", alg_cut_netF="mlp_sample",
-    alg_cut_netF_nc=256, alg_cut_nce_T=0.07, alg_cut_num_patches=256, alg_cut_flip_equivariance=False, alg_cut_MSE_idt=False,
+    alg_cut_netF_nc=256, alg_cut_nce_T=0.07, alg_cut_HDCE_gamma=1.0, alg_cut_HDCE_gamma_min=1.0, alg_cut_num_patches=256, alg_cut_flip_equivariance=False, alg_cut_MSE_idt=False,
     alg_cut_supervised_loss=[""], alg_gan_lambda=1.0, train_gan_mode="lsgan", D_netDs=["basic"], D_ndf=64, D_n_layers=3,
     D_dropout=False, D_spectral=False, dataaug_D_label_smooth=False, dataaug_D_noise=0.0, dataaug_APA=False,
     dataaug_D_diffusion=False, train_semantic_mask=False, train_semantic_cls=False, train_mask_out_mask=False,
@@ -48,6 +51,24 @@ class _ScaleGradFn(JGFunction):
 
 
 FORK_GAN_DEFAULT = True
+
+
+def check_nce_options(opt):
+    """the contrastive-loss options of cut_model.py:39-137 that this build accepts; returns True for SRC_hDCE.  Host-only (no device)."""
+    for k in ("alg_cut_nce_loss", "alg_cut_lambda_SRC", "alg_cut_HDCE_gamma"):
+        if not hasattr(opt, k):
+            setattr(opt, k, CUT_DEFAULTS[k])
+    if opt.alg_cut_nce_loss not in ("monce", "patchnce", "SRC_hDCE"):
+        raise NotImplementedError(f"alg_cut_nce_loss={opt.alg_cut_nce_loss!r}")
+    hdce = opt.alg_cut_nce_loss == "SRC_hDCE"
+    if hdce and not float(opt.alg_cut_HDCE_gamma) > 0.0:
+        raise ValueError(f"alg_cut_HDCE_gamma={opt.alg_cut_HDCE_gamma!r}: the hDCE weights are exp(similarity / gamma), gamma must be > 0")
+    if opt.alg_cut_lambda_SRC > 0:
+        if not hdce:      # the reference builds its SRC criterion only with SRC_hDCE and fails on the missing attribute otherwise
+            raise NotImplementedError("alg_cut_lambda_SRC > 0 needs alg_cut_nce_loss='SRC_hDCE'")
+        # cut_model.py:734-761: loss_G_SRC is computed, reset to 0.0 (alg_cut_MSE_idt off) and never added to loss_G_tot
+        warnings.warn("alg_cut_lambda_SRC > 0: as in the reference, the SRC (JSD) term does not enter the update; only the hDCE weights do")
+    return hdce
 
 
 class CUTModel(BaseModel):
@@ -72,14 +93,14 @@ class CUTModel(BaseModel):
                                       "depth / mask / sam / temporal discriminators need pretrained networks)")
         if opt.alg_cut_netF != "mlp_sample":
             raise NotImplementedError(f"alg_cut_netF={opt.alg_cut_netF!r}")
-        if opt.alg_cut_nce_loss not in ("monce", "patchnce"):
-            raise NotImplementedError(f"alg_cut_nce_loss={opt.alg_cut_nce_loss!r}")
+        self.hdce = check_nce_options(opt)
         for flag in ("model_multimodal", "alg_cut_flip_equivariance", "alg_cut_MSE_idt", "train_semantic_mask", "train_semantic_cls",
                      "train_mask_out_mask", "dataaug_APA", "dataaug_D_diffusion"):
             if getattr(opt, flag, False):
                 raise NotImplementedError(f"{flag} is outside the SURVEY.md 8 hot path")
-        if opt.alg_cut_lambda_SRC > 0 or [s for s in opt.alg_cut_supervised_loss if s] or opt.dataaug_D_noise > 0:
-            raise NotImplementedError("SRC / supervised / noisy-D terms are outside the built path")
+        if [s for s in opt.alg_cut_supervised_loss if s] or opt.dataaug_D_noise > 0:
+            raise NotImplementedError("supervised / noisy-D terms are outside the built path")
+        self.loss_G_SRC = 0.0      # cut_model.py:760: reset on every iteration without alg_cut_MSE_idt, never part of loss_G_tot
         # options that select ANOTHER network than the one built here must not be dropped silently: the generator /
         # PatchGAN below are the InstanceNorm, no-dropout, no-spectral-norm variants of gan_networks.define_G / define_D
         for name, built in (("G_dropout", False), ("D_dropout", False), ("D_spectral", False), ("G_spectral", False),
@@ -131,7 +152,7 @@ class CUTModel(BaseModel):
             # iteration: they feed only the metrics, but they consume host random draws BEFORE the fake pool does
             self.real_A_pool, self.real_B_pool = ImagePool(opt.train_pool_size), ImagePool(opt.train_pool_size)
             self.fake_B_pool = ImagePool(opt.train_pool_size)
-            crit = MoNCELoss if opt.alg_cut_nce_loss == "monce" else PatchNCELoss
+            crit = PatchHDCELoss if self.hdce else MoNCELoss if opt.alg_cut_nce_loss == "monce" else PatchNCELoss
             self.criterionNCE = [crit(opt) for _ in self.nce_layers]
             kw = dict(lr=opt.train_G_lr, betas=(opt.train_beta1, opt.train_beta2), weight_decay=opt.train_optim_weight_decay,
                       eps=opt.train_optim_eps)
@@ -322,7 +343,10 @@ class CUTModel(BaseModel):
             n = B * Pl
             q = torch.cat([rows[i][0] for i in ls], dim=0)                           # [layer][term][B * P_l] problems
             k = torch.cat([rows[i][1] for i in ls], dim=0)
-            loss = ops.patch_nce_loss(q, k, 2 * len(ls) * B, T, P, monce).view(len(ls), 2, n)
+            if self.hdce:      # problems [layer][term][B]: the NCE term (term 0) is weighted, the identity term is not (cut_model.py:734-766)
+                loss = ops.patch_hdce_loss(q, k, 2 * len(ls) * B, T, o.alg_cut_HDCE_gamma, 2 * B, B).view(len(ls), 2, n)
+            else:
+                loss = ops.patch_nce_loss(q, k, 2 * len(ls) * B, T, P, monce).view(len(ls), 2, n)
             return loss.mean(dim=2).sum(dim=0) * o.alg_cut_lambda_NCE
 
         # (round 6, measured and removed: the smaller patch-count set on a forked third stream inside the graphs -- 20.0 -> 23.5 ms,
@@ -339,10 +363,10 @@ class CUTModel(BaseModel):
         if self._batched_nce():
             return self.compute_G_loss_cut_batched()
         fq, fk = self.calculate_feats(self.real_A, self.fake_B)
-        self.loss_G_NCE = self.calculate_NCE_loss(fq, fk) if self.opt.alg_cut_lambda_NCE > 0.0 else 0.0
+        self.loss_G_NCE = self.calculate_NCE_loss(fq, fk, weighted=True) if self.opt.alg_cut_lambda_NCE > 0.0 else 0.0
         if self.opt.alg_cut_nce_idt and self.opt.alg_cut_lambda_NCE > 0.0:
             fq, fk = self.calculate_feats(self.real_B, self.idt_B)
-            self.loss_G_NCE_Y = self.calculate_NCE_loss(fq, fk)
+            self.loss_G_NCE_Y = self.calculate_NCE_loss(fq, fk, weighted=False)
             loss_NCE_both = (self.loss_G_NCE + self.loss_G_NCE_Y) * 0.5
         else:
             loss_NCE_both = self.loss_G_NCE
@@ -363,11 +387,11 @@ class CUTModel(BaseModel):
         feat_q_pool, _ = netF(feat_q, self.opt.alg_cut_num_patches, sample_ids, self.feat_channels)
         return feat_q_pool, feat_k_pool
 
-    def calculate_NCE_loss(self, feat_q_pool, feat_k_pool):
-        """:889-909."""
+    def calculate_NCE_loss(self, feat_q_pool, feat_k_pool, weighted=True):
+        """:889-909.  `weighted` (SRC_hDCE only): the NCE(G(X), X) term runs with the hDCE weights, the identity term with weight=None (:734-766)."""
         total = 0.0
         for f_q, f_k, crit in zip(feat_q_pool, feat_k_pool, self.criterionNCE):
-            loss = crit(feat_q=f_q, feat_k=f_k, current_batch=self.get_current_batch_size()) * self.opt.alg_cut_lambda_NCE
+            loss = crit(feat_q=f_q, feat_k=f_k, current_batch=self.get_current_batch_size(), weighted=weighted) * self.opt.alg_cut_lambda_NCE
             total = total + loss.mean()
         return total / len(self.nce_layers)
 

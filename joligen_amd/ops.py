@@ -1344,6 +1344,89 @@ def patch_nce_loss(q, k, nimg, T, num_patches, monce=False):
     return _PatchNCEFn.apply(q, k, nimg, float(T), float(num_patches - 1), bool(monce))
 
 
+def _hdce_gram(k, nimg, P, D, wperiod, wcount):
+    """k k^T of the problems whose weights are needed: the leading `wcount` problems when there is a single weighted run, else every problem in
+    ONE launch (the weighted runs are not a strided batch; the kernel never reads the Gram matrix of an unweighted problem)"""
+    if wcount < 1:
+        return None
+    ng = min(wcount, nimg) if wperiod >= nimg else nimg
+    G = torch.empty((ng, P, P), device=k.device, dtype=torch.float32)
+    sgemm(k, k, G, P, P, D, (D, 1), (D, 1), (P, 1), ng, (P * D, P * D, P * P))
+    return G
+
+
+def _hdce_check(nimg, R, gamma, wperiod, wcount):
+    if nimg < 1 or R % nimg or not gamma > 0 or wperiod < 1 or not 0 <= wcount <= wperiod:
+        raise ValueError(f"patch_hdce: nimg={nimg} rows={R} gamma={gamma} wperiod={wperiod} wcount={wcount}")
+
+
+class _PatchHDCEFn(JGFunction):
+    """Per-patch SRC_hDCE loss (NCE/SRC.py:46-75 weights, NCE/hDCE.py:16-38).  q, k: [nimg*P, D] fp32.  The weights come from the key
+    Gram matrix inside the kernel (detached, never stored); the value is the cross-entropy of [l_pos | weighted l_neg] / T, the gradient
+    that of logsumexp(weighted l_neg / T) - l_pos / T; k is detached in the positive logit but NOT in the negative logits."""
+
+    @staticmethod
+    def forward(ctx, q, k, nimg, T, gamma, wperiod, wcount):
+        _require_cuda(q, k)
+        q, k = q.contiguous(), k.contiguous()
+        R, D = q.shape
+        _hdce_check(nimg, R, gamma, wperiod, wcount)
+        P = R // nimg
+        S = torch.empty((nimg, P, P), device=q.device, dtype=torch.float32)
+        sgemm(q, k, S, P, P, D, (D, 1), (D, 1), (P, 1), nimg, (P * D, P * D, P * P))
+        G = _hdce_gram(k, nimg, P, D, wperiod, wcount)
+        loss = torch.empty(R, device=q.device, dtype=torch.float32)
+        stats = torch.empty((3, R), device=q.device, dtype=torch.float32)
+        check(_lib.lib().jg_nce_hdce(S.data_ptr(), _p(G), stats.data_ptr(), loss.data_ptr(), None, None, None, None, nimg, P, T, gamma, wperiod,
+                                     wcount, _st()), "jg_nce_hdce")
+        ctx.save_for_backward(q, k, S, G, stats)
+        ctx.cfg = (nimg, P, D, T, gamma, wperiod, wcount)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss):
+        q, k, S, G, stats = ctx.saved_tensors
+        nimg, P, D, T, gamma, wperiod, wcount = ctx.cfg
+        L = _lib.lib()
+        dloss = dloss.contiguous().float()
+        dS = torch.empty_like(S)
+        gpos = torch.empty(nimg * P, device=q.device, dtype=torch.float32)
+        check(L.jg_nce_hdce(S.data_ptr(), _p(G), stats.data_ptr(), None, dS.data_ptr(), gpos.data_ptr(), dloss.data_ptr(), None, nimg, P, T, gamma,
+                            wperiod, wcount, _st()), "jg_nce_hdce")
+        dk = None
+        if ctx.needs_input_grad[1]:
+            dk = torch.empty_like(k)
+            sgemm(dS, q, dk, P, D, P, (1, P), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
+        dq = torch.empty_like(q)
+        sgemm(dS, k, dq, P, D, P, (P, 1), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
+        check(L.jg_row_axpy(dq.data_ptr(), gpos.data_ptr(), k.data_ptr(), nimg * P, D, _st()), "jg_row_axpy")
+        return dq, dk, None, None, None, None, None
+
+
+def patch_hdce_loss(q, k, nimg, T, gamma, wperiod=1, wcount=1):
+    """SRC_Loss weights + PatchHDCELoss (NCE/SRC.py, NCE/hDCE.py): per-patch loss [nimg*P].  Problem b uses the weights iff
+    (b % wperiod) < wcount; the others are the reference's `weight=None` mode (w == 1)."""
+    if TORCH_OPS_BOUNDARY:
+        return torch.ops.jg355.patch_hdce(q, k, int(nimg), float(T), float(gamma), int(wperiod), int(wcount))[0]
+    return _PatchHDCEFn.apply(q, k, int(nimg), float(T), float(gamma), int(wperiod), int(wcount))
+
+
+def hdce_weights(k, nimg, gamma):
+    """the hDCE weights [nimg, P, P] of SRC_Loss(only_weight=True) with a zero diagonal (tests / inspection: training never stores them)"""
+    _require_cuda(k)
+    k = k.detach().contiguous()
+    R, D = k.shape
+    _hdce_check(nimg, R, gamma, 1, 1)
+    P = R // nimg
+    G = _hdce_gram(k, nimg, P, D, 1, 1)
+    W = torch.empty_like(G)
+    scratch = torch.empty((4, R), device=k.device, dtype=torch.float32)
+    check(_lib.lib().jg_nce_hdce(G.data_ptr(), G.data_ptr(), scratch.data_ptr(), scratch[3].data_ptr(), None, None, None, W.data_ptr(), nimg, P, 1.0,
+                                 float(gamma), 1, 1, _st()), "jg_nce_hdce")
+    return W
+
+
 GAN_MODES = {"lsgan": 0, "vanilla": 1, "wgangp": 2}
 
 

@@ -15,6 +15,7 @@ tests/test_gpu_5_cutloss.py::test_cut_step_through_torch_ops holds the two forms
   dilate2d                                   zero insertion (ConvTranspose2d = dilate + stride-1 conv on the flipped weights; stride-s dgrad)
   act / act_bwd                              stand-alone ReLU / LeakyReLU / Tanh
   gather_patches / scatter_patches, l2_normalize / _bwd, patch_nce / patch_nce_bwd      PatchSampleF + PatchNCE / MoNCE (Sinkhorn inside)
+  patch_hdce / patch_hdce_bwd                SRC_hDCE: weights from the key Gram matrix + weighted contrastive loss, one fused kernel
   gan_loss, hinge_loss                       GANLoss (lsgan / vanilla / wgangp) and the projected hinge; return (loss, d loss / d pred)
   spectral_weight / _bwd                     torch.nn.utils.spectral_norm: one power iteration, W / sigma; gradient through 1 / sigma
   bilinear2 / bilinear2_bwd                  F.interpolate(mode="bilinear", align_corners=...)
@@ -580,6 +581,74 @@ def _nce_backward(ctx, dloss, *unused):
 
 
 patch_nce.register_autograd(_nce_backward, setup_context=_nce_setup)
+
+
+@op("jg355::patch_hdce", mutates_args=())
+def patch_hdce(q: T, k: T, nimg: int, temp: float, gamma: float, wperiod: int, wcount: int) -> Tuple[T, T, T, T]:
+    """per-patch SRC_hDCE loss (NCE/SRC.py:46-75, NCE/hDCE.py:16-38): q, k [nimg * P, D] fp32; problem b is weighted iff (b % wperiod) < wcount
+    -> (loss [nimg * P], logits S, key Gram matrix G (empty with wcount == 0), stats [3, nimg * P] = m | A | rinv for the backward)"""
+    q, k = q.contiguous(), k.contiguous()
+    R, D = q.shape
+    ops._hdce_check(nimg, R, gamma, wperiod, wcount)
+    P = R // nimg
+    S = torch.empty((nimg, P, P), device=q.device, dtype=torch.float32)
+    sgemm(q, k, S, P, P, D, (D, 1), (D, 1), (P, 1), nimg, (P * D, P * D, P * P))
+    G = ops._hdce_gram(k, nimg, P, D, wperiod, wcount)
+    loss = torch.empty(R, device=q.device, dtype=torch.float32)
+    stats = torch.empty((3, R), device=q.device, dtype=torch.float32)
+    check(_lib.lib().jg_nce_hdce(S.data_ptr(), _p(G), stats.data_ptr(), loss.data_ptr(), None, None, None, None, nimg, P, temp, gamma, wperiod, wcount,
+                                 _st()), "jg_nce_hdce")
+    return loss, S, (_z(q) if G is None else G), stats
+
+
+def _hdce_ng(nimg, wperiod, wcount):
+    return 0 if wcount < 1 else (min(wcount, nimg) if wperiod >= nimg else nimg)
+
+
+@patch_hdce.register_fake
+def _(q, k, nimg, temp, gamma, wperiod, wcount):
+    R = q.shape[0]
+    P = R // nimg
+    ng = _hdce_ng(nimg, wperiod, wcount)
+    return q.new_empty((R,)), q.new_empty((nimg, P, P)), (q.new_empty((ng, P, P)) if ng else q.new_empty((0,))), q.new_empty((3, R))
+
+
+@op("jg355::patch_hdce_bwd", mutates_args=())
+def patch_hdce_bwd(q: T, k: T, S: T, G: T, stats: T, dloss: T, nimg: int, temp: float, gamma: float, wperiod: int, wcount: int) -> Tuple[T, T]:
+    L = _lib.lib()
+    R, D = q.shape
+    P = R // nimg
+    dloss = dloss.contiguous().float()
+    dS = torch.empty_like(S)
+    gpos = torch.empty(R, device=q.device, dtype=torch.float32)
+    check(L.jg_nce_hdce(S.data_ptr(), G.data_ptr() if G.numel() else None, stats.data_ptr(), None, dS.data_ptr(), gpos.data_ptr(), dloss.data_ptr(), None,
+                        nimg, P, temp, gamma, wperiod, wcount, _st()), "jg_nce_hdce")
+    dk = torch.empty_like(k)
+    sgemm(dS, q, dk, P, D, P, (1, P), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
+    dq = torch.empty_like(q)
+    sgemm(dS, k, dq, P, D, P, (P, 1), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
+    check(L.jg_row_axpy(dq.data_ptr(), gpos.data_ptr(), k.data_ptr(), R, D, _st()), "jg_row_axpy")
+    return dq, dk
+
+
+@patch_hdce_bwd.register_fake
+def _(q, k, S, G, stats, dloss, nimg, temp, gamma, wperiod, wcount):
+    return torch.empty_like(q), torch.empty_like(k)
+
+
+def _hdce_setup(ctx, inputs, output):
+    q, k, nimg, temp, gamma, wperiod, wcount = inputs
+    ctx.save_for_backward(q, k, *output[1:])
+    ctx.cfg = (nimg, temp, gamma, wperiod, wcount)
+
+
+def _hdce_backward(ctx, dloss, *unused):
+    q, k, S, G, stats = ctx.saved_tensors
+    dq, dk = torch.ops.jg355.patch_hdce_bwd(q, k, S, G, stats, dloss, *ctx.cfg)
+    return dq, dk, None, None, None, None, None
+
+
+patch_hdce.register_autograd(_hdce_backward, setup_context=_hdce_setup)
 
 
 # ---- GAN objectives: (loss, d loss / d pred) -------------------------------------------------------------------------------------------------
