@@ -588,6 +588,13 @@ int jg_ddpm_p_sample(int dtype, float* y_t, const float* y_cond, const void* noi
  *   cm_loss    : lambda * mean(w[b] * pseudo_huber(mask*pred, mask*target)) with pred/target formed on the fly from
  *                the two UNet outputs, and dL/dF_next in the same pass (compute_cm_loss cm_model.py:353-375,
  *                pseudo_huber_loss :27-43; the mask multiplies AS IS, like the reference); loss accumulates (zero it)
+ *   ect_loss   : easy consistency tuning (compute_ect_loss cm_model.py:412-442): with pred/target and d = m*pred - m*target as in
+ *                cm_loss, S_b = sum_{c,h,w} d^2, loss = lambda * mean_b((sqrt(S_b + c^2) - c) / dt[b]) (dt = t - r) and
+ *                dFn = grad_scale * lambda/B * d / (sqrt(S_b + c^2) * dt[b]) * m * co_n[b] (0 in the pad channels and where m == 0).
+ *                Two launches on `s`: per-block partial sums of d^2 into `ws`, then the gradient and the scalar.  No atomics and
+ *                nothing to zero: loss and dFn are overwritten and are the same bits on every run.  `ws` is the caller's, at least
+ *                B * min(ceil(H*W / 256), 64) floats (`ws_floats` says how many it holds).  Cpad must be 8 (one 16-byte access per
+ *                pixel; JG_ERR_UNSUPPORTED otherwise) and Fn, Fc, dFn 16-byte aligned.
  *   noise_level_embedding : [sin | cos](sigma * W * 2 pi)  (NoiseLevelEmbedding.forward :276-280) */
 int jg_cm_noisy(int dtype, const float* x, const float* noise, const float* sigma, const int64_t* mask, const float* cond,
                 float* out_nchw, void* out_nhwc, int B, int C, int Ccond, int H, int W, int Cpad, jg_stream_t s);
@@ -596,6 +603,10 @@ int jg_cm_combine(int dtype, const float* noisy, const void* F, const float* csk
 int jg_cm_loss(int dtype, const void* Fn, const void* Fc, const float* noisy_n, const float* noisy_c, const float* cs_n,
                const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask, const float* w, float* loss,
                void* dFn, int B, int C, int H, int W, int Cpad, float c_huber, float lambda, float grad_scale, jg_stream_t s);
+int jg_ect_loss(int dtype, const void* Fn, const void* Fc, const float* noisy_n, const float* noisy_c, const float* cs_n,
+                const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask, const float* dt, float* ws,
+                int64_t ws_floats, float* loss, void* dFn, int B, int C, int H, int W, int Cpad, float c, float lambda,
+                float grad_scale, jg_stream_t s);
 int jg_noise_level_embedding(const float* sigma, const float* W, float* emb, int Bn, int half, jg_stream_t s);
 /* gradient of the embedding with respect to W, ACCUMULATED into dW (the reference trains W: set_requires_grad(net, True),
  * base_model.py:1196-1217) */

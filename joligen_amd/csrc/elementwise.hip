@@ -824,6 +824,114 @@ __global__ __launch_bounds__(256) void cm_loss_kernel(const T* __restrict__ Fn, 
   if (threadIdx.x == 0) atomicAdd(loss, (s_part[0] + s_part[1] + s_part[2] + s_part[3]) * invN * lambda);
 }
 
+// Easy-consistency-tuning loss with its gradient (compute_ect_loss, cm_model.py:412-442):
+//   pred / target as in cm_loss_kernel,  d = m*pred - m*target (m = the label mask AS IS),  S_b = sum_{c,h,w} d^2,
+//   loss = lambda * mean_b( (sqrt(S_b + c^2) - c) / dt_b ),   dF_n = grad_scale * lambda/B * d / (sqrt(S_b + c^2) * dt_b) * m * co_n
+// Every gradient element needs its sample's whole sum, so two kernels on one stream: ect_partial_kernel leaves one partial sum per
+// block in the caller's workspace (every slot written: nothing to zero), ect_grad_kernel adds its sample's partials in index order,
+// recomputes d and writes the gradient; block (0, 0) also writes the scalar.  No atomics: the same bits on every run.
+// grid = (blocks per sample, B); one pixel per thread and trip: one 16-byte load of each UNet output, the fp32 NCHW planes read along
+// the pixel index, one 16-byte store.
+constexpr int ECT_MAX_BLOCKS = 64;   // per sample; the workspace holds B * ECT_MAX_BLOCKS floats at most
+
+__device__ __forceinline__ void two_sum(float a, float b, float& s, float& e) {
+#pragma clang fp contract(off)
+  s = a + b;
+  const float bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+// (cs_n*xn + co_n*fn) - (cs_c*xc + co_c*fc) to fp32 relative accuracy: the products and the three sums carry their rounding errors
+// along (fma residuals, two_sum), so the difference keeps its digits where student and teacher nearly agree -- every r = 0 sample late
+// in training -- and the 16-bit gradient is the rounded exact one there too.
+__device__ __forceinline__ float ect_diff(float cs_n, float xn, float co_n, float fn, float cs_c, float xc, float co_c, float fc) {
+#pragma clang fp contract(off)
+  const float a = cs_n * xn, b = co_n * fn, c = cs_c * xc, e = co_c * fc;
+  const float lo = (fmaf(cs_n, xn, -a) + fmaf(co_n, fn, -b)) - (fmaf(cs_c, xc, -c) + fmaf(co_c, fc, -e));
+  float s1, e1, s2, e2, s, e3;
+  two_sum(a, b, s1, e1);
+  two_sum(c, e, s2, e2);
+  two_sum(s1, -s2, s, e3);
+  return s + ((e3 + (e1 - e2)) + lo);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ect_partial_kernel(const T* __restrict__ Fn, const T* __restrict__ Fc,
+                                                          const float* __restrict__ noisy_n, const float* __restrict__ noisy_c,
+                                                          const float* __restrict__ cs_n, const float* __restrict__ co_n,
+                                                          const float* __restrict__ cs_c, const float* __restrict__ co_c,
+                                                          const int64_t* __restrict__ mask, float* __restrict__ partial, int C,
+                                                          long HW) {
+  __shared__ float s_part[4];
+  const int b = blockIdx.y;
+  const float csn = cs_n[b], con = co_n[b], csc = cs_c[b], coc = co_c[b];
+  float acc = 0.f;
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < HW; p += gridDim.x * 256L) {
+    const long i = (long)b * HW + p;
+    const float m = mask ? (float)mask[i] : 1.0f;
+    float fn[8], fc[8];
+    unpack8<T>(reinterpret_cast<const uint4*>(Fn)[i], fn);
+    unpack8<T>(reinterpret_cast<const uint4*>(Fc)[i], fc);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      if (c < C) {
+        const long q = ((long)b * C + c) * HW + p;
+        const float d = m * ect_diff(csn, noisy_n[q], con, fn[c], csc, noisy_c[q], coc, fc[c]);
+        acc = fmaf(d, d, acc);
+      }
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[(long)b * gridDim.x + blockIdx.x] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+}
+
+__device__ __forceinline__ float ect_sample_sum(const float* __restrict__ partial, int b, int nblk) {
+  float S = 0.f;
+  for (int k = 0; k < nblk; ++k) S += partial[(long)b * nblk + k];
+  return S;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ect_grad_kernel(const T* __restrict__ Fn, const T* __restrict__ Fc,
+                                                       const float* __restrict__ noisy_n, const float* __restrict__ noisy_c,
+                                                       const float* __restrict__ cs_n, const float* __restrict__ co_n,
+                                                       const float* __restrict__ cs_c, const float* __restrict__ co_c,
+                                                       const int64_t* __restrict__ mask, const float* __restrict__ dt,
+                                                       const float* __restrict__ partial, float* __restrict__ loss,
+                                                       T* __restrict__ dFn, int B, int C, long HW, float c, float lambda,
+                                                       float grad_scale) {
+  __shared__ float s_part[4];
+  const int b = blockIdx.y, nblk = gridDim.x;
+  const float csn = cs_n[b], con = co_n[b], csc = cs_c[b], coc = co_c[b];
+  const float g = grad_scale * lambda / (float)B / (sqrtf(ect_sample_sum(partial, b, nblk) + c * c) * dt[b]) * con;
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < HW; p += gridDim.x * 256L) {
+    const long i = (long)b * HW + p;
+    const float m = mask ? (float)mask[i] : 1.0f;
+    float fn[8], fc[8];
+    unpack8<T>(reinterpret_cast<const uint4*>(Fn)[i], fn);
+    unpack8<T>(reinterpret_cast<const uint4*>(Fc)[i], fc);
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) {
+      float gout = 0.f;
+      if (ch < C && m != 0.f) {
+        const long q = ((long)b * C + ch) * HW + p;
+        gout = g * (m * ect_diff(csn, noisy_n[q], con, fn[ch], csc, noisy_c[q], coc, fc[ch])) * m;
+      }
+      fn[ch] = gout;
+    }
+    reinterpret_cast<uint4*>(dFn)[i] = pack8<T>(fn);
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0) {
+    float acc = 0.f;
+    for (int bb = threadIdx.x; bb < B; bb += 256) acc += (sqrtf(ect_sample_sum(partial, bb, nblk) + c * c) - c) / dt[bb];
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) *loss = ((s_part[0] + s_part[1]) + (s_part[2] + s_part[3])) * lambda / (float)B;
+  }
+}
+
 // NoiseLevelEmbedding (cm_generator.py:276-280): h = sigma * W * 2 * pi; [sin(h) | cos(h)]
 __global__ void noise_level_embedding_kernel(const float* __restrict__ sigma, const float* __restrict__ W, float* __restrict__ emb,
                                              int Bn, int half) {
@@ -1032,6 +1140,27 @@ extern "C" int jg_cm_loss(int dtype, const void* Fn, const void* Fc, const float
   JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((cm_loss_kernel<T>), dim3(loss_grid(total, 256, 1024)), dim3(256), 0, (hipStream_t)s,
                                               (const T*)Fn, (const T*)Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, w, loss,
                                               (T*)dFn, B, C, H * W, Cpad, c_huber, lambda, grad_scale););
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+extern "C" int jg_ect_loss(int dtype, const void* Fn, const void* Fc, const float* noisy_n, const float* noisy_c,
+                           const float* cs_n, const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask,
+                           const float* dt, float* ws, int64_t ws_floats, float* loss, void* dFn, int B, int C, int H, int W, int Cpad,
+                           float c, float lambda, float grad_scale, jg_stream_t s) {
+  if (!Fn || !Fc || !noisy_n || !noisy_c || !cs_n || !co_n || !cs_c || !co_c || !dt || !ws || !loss || !dFn || B < 1 || B > 65535 ||
+      C < 1 || H < 1 || W < 1 || Cpad < C || !(c >= 0.f))
+    return JG_ERR_BAD_ARG;
+  if (Cpad != 8) return JG_ERR_UNSUPPORTED;             // one 16-byte access per pixel is the whole channel vector
+  if (((uintptr_t)Fn | (uintptr_t)Fc | (uintptr_t)dFn) & 15) return JG_ERR_BAD_ARG;
+  const long HW = (long)H * W;
+  const long need = (HW + 255) / 256;
+  const int nblk = (int)(need < ECT_MAX_BLOCKS ? need : ECT_MAX_BLOCKS);
+  if (ws_floats < (long)B * nblk) return JG_ERR_BAD_ARG;
+  JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((ect_partial_kernel<T>), dim3(nblk, B), dim3(256), 0, (hipStream_t)s, (const T*)Fn,
+                                              (const T*)Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, ws, C, HW);
+                    hipLaunchKernelGGL((ect_grad_kernel<T>), dim3(nblk, B), dim3(256), 0, (hipStream_t)s, (const T*)Fn, (const T*)Fc,
+                                       noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, dt, ws, loss, (T*)dFn, B, C, HW, c, lambda,
+                                       grad_scale););
   JG_CHECK_LAUNCH();
   return JG_OK;
 }

@@ -1,17 +1,19 @@
 """cm_model (consistency model) training step on MI355X: mirror of /root/reference/models/cm_model.py
 (`__init__` :115-263, `set_input` :265-351 (inpainting / pix2pix, cond_image_creation="y_t"), `compute_cm_loss`
-:353-375 without perceptual terms, `pseudo_huber_loss` :27-43) and models/diffusion_networks.py `define_G`
+:353-375 and `compute_ect_loss` :412-502 without perceptual terms, `pseudo_huber_loss` :27-43) and models/diffusion_networks.py `define_G`
 (:24-139,377-383) for `model_type="cm"`, `G_netG="unet_mha"`.
 
 The step = 2 UNet forwards (student with gradient, teacher without) + 1 backward on the same fused schedule and
-kernels as palette_model; the consistency loss and its gradient are one fused kernel (`jg_cm_loss`).
+kernels as palette_model; the consistency loss and its gradient are one fused kernel (`jg_cm_loss`).  With
+`alg_ddpm_ft_mode="ect"` (easy consistency tuning) the two passes run at the noise levels t and r(t) and the loss is the per-sample
+L2 norm of `jg_ect_loss`; the tick / stage schedule of the reference advances on the host (`ect_tick`).
 """
 from __future__ import annotations
 
 import torch
 
 from .. import ops
-from ..modules.cm_generator import CMGenerator
+from ..modules.cm_generator import CMGenerator, check_ft_mode
 from ..modules.unet_generator_attn import UNet
 from .base_model import BaseModel, NetworkGroup
 
@@ -37,6 +39,19 @@ def define_G_cm(opt):
     return CMGenerator(cm_model=model, sampling_method="", image_size=opt.data_crop_size, G_ngf=opt.G_ngf, opt=opt)
 
 
+def ect_tick(state, batch_size, net=None):
+    """the tick / stage bookkeeping at the end of compute_ect_loss (cm_model.py:480-502) on a plain dict with cur_nimg, cur_tick,
+    tick_start_nimg, kimg_per_tick: every kimg_per_tick * 1000 images one tick, and `net.update_stage(cur_tick)`.  Host only."""
+    state["cur_nimg"] += batch_size
+    if state["cur_nimg"] >= state["tick_start_nimg"] + state["kimg_per_tick"] * 1000:
+        state["cur_tick"] += 1
+        state["tick_start_nimg"] = state["cur_nimg"]
+        if net is not None:
+            net.update_stage(state["cur_tick"])
+        return True
+    return False
+
+
 class CMModel(BaseModel):
     overlap_exchange = True   # one backward per optimizer step: the gradient all-reduce starts inside the backward
 
@@ -49,6 +64,7 @@ class CMModel(BaseModel):
             raise NotImplementedError("only alg_diffusion_cond_image_creation='y_t' is implemented")
         if [p for p in getattr(opt, "alg_cm_perceptual_loss", [""]) if p]:
             raise NotImplementedError("LPIPS / DISTS perceptual terms need pretrained networks (not available offline)")
+        self.ft_mode = check_ft_mode(opt)                                                 # cm_model.py:119
         self.total_t = opt.alg_cm_num_steps * opt.train_batch_size                       # cm_model.py:129-131
         opt.alg_palette_sampling_method = ""                                              # :193-198
         opt.alg_diffusion_cond_embed = opt.alg_diffusion_cond_image_creation
@@ -63,14 +79,18 @@ class CMModel(BaseModel):
             self.optimizers.append(self.optimizer_G)
         self.loss_names_G = ["G_tot"]
         self.loss_names = list(self.loss_names_G)
-        self.group_G = NetworkGroup(networks_to_optimize=["G_A"], forward_functions=[], backward_functions=["compute_cm_loss"],
+        backward_fn = "compute_ect_loss" if self.ft_mode == "ect" else "compute_cm_loss"  # :228
+        self.group_G = NetworkGroup(networks_to_optimize=["G_A"], forward_functions=[], backward_functions=[backward_fn],
                                     loss_names_list=["loss_names_G"], optimizer=["optimizer_G"], loss_backward=["loss_G_tot"],
                                     networks_to_ema=["G_A"])
         self.networks_groups = [self.group_G]
         self.iter_calculator_init()
-        self.rng_injection = None  # parity runs: callable(sigmas on the host) -> (noise, timesteps)
+        self.rng_injection = None  # parity runs: callable(batch size) -> (noise, timesteps); ft_mode "ect": (noise, rnd_normal)
         # visuals (cm_model.py:139-185)
-        self.gen_visual_names = ["gt_image_", "y_t_", "next_noisy_x_", "current_noisy_x_", "mask_", "output_"]
+        noisy = ["t_noisy_x_", "r_noisy_x_"] if self.ft_mode == "ect" else ["next_noisy_x_", "current_noisy_x_"]
+        self.gen_visual_names = ["gt_image_", "y_t_"] + noisy + ["mask_", "output_"]
+        if self.ft_mode == "ect":       # tick counters (:257-263); like the reference's, not part of a checkpoint
+            self.ect_state = dict(cur_tick=0, cur_nimg=0, tick_start_nimg=0, kimg_per_tick=50)
         for k in range(opt.train_batch_size):
             self.visual_names.append([n + str(k) for n in self.gen_visual_names])
         self.visual_names.append([])
@@ -99,6 +119,18 @@ class CMModel(BaseModel):
         self.loss_G_tot = ops.cm_loss(r["F_next"], r["F_cur"], r["next_noisy_x"], r["current_noisy_x"], r["cs_n"], r["co_n"],
                                       r["cs_c"], r["co_c"], self.mask, r["loss_weights"], lam=self.opt.alg_diffusion_lambda_G,
                                       grad_scale=self.loss_scale)
+
+    # cm_model.py:412-442,480-502
+    def compute_ect_loss(self):
+        net = self._net("G_A")
+        noise = rnd_normal = None
+        if self.rng_injection is not None:
+            noise, rnd_normal = self.rng_injection(self.gt_image.shape[0])
+        r = net.forward_nhwc(self.gt_image, self.total_t, self.mask, self.cond_image, noise, rnd_normal=rnd_normal)
+        self.t_noisy_x, self.r_noisy_x = r["t_noisy_x"], r["r_noisy_x"]
+        self.loss_G_tot = ops.ect_loss(r["F_next"], r["F_cur"], r["t_noisy_x"], r["r_noisy_x"], r["cs_n"], r["co_n"], r["cs_c"], r["co_c"],
+                                       self.mask, r["t"] - r["r"], lam=self.opt.alg_diffusion_lambda_G, grad_scale=self.loss_scale)
+        ect_tick(self.ect_state, self.gt_image.shape[0], net)
 
     # cm_model.py:504-657
     SAMPLING_SIGMAS = (80.0, 24.4, 5.84, 0.9, 0.661)

@@ -1,13 +1,15 @@
 """Consistency-model generator on the HIP ops: mirror of /root/reference/models/modules/cm_generator.py
 (`NoiseLevelEmbedding` :255-280, schedules :32-164, scalings :167-252, `CMGenerator` :283-326,
-`cm_forward` :367-386, `forward` :388-502 for `alg_ddpm_ft_mode == "cm"`).
+`cm_forward` :367-386, `forward` :388-502; `alg_ddpm_ft_mode == "ect"`: `_train` scalings :189-252, `t_to_r_sigmoid` /
+`update_stage` :315-340, `ect_forward` :342-365, the ECT branch of `forward` :396-442).
 
 state_dict keys are the reference's: `cm_model.<unet...>`, `cm_cond_embed.W`,
 `cm_cond_embed.projection.{0,2}.{weight,bias}`.
 
 Per step the UNet runs twice on the fused schedule (unet_exec.py): the student on x + sigma_{n+1} eps (with
-gradient) and the teacher on x + sigma_n eps (same weights, no gradient).  The ECT branch (:396-435) and
-`restoration` (:504-554) are not part of the training hot path built here.
+gradient) and the teacher on x + sigma_n eps (same weights, no gradient).  Easy consistency tuning ("ect") is the same two passes
+at the noise levels t (student) and r = t_to_r(t) <= t (teacher) with the `_train` scalings; at r = 0 those are exactly (1, 0) and the
+teacher's output is x itself.  `restoration` (:504-554) always samples with `cm_forward`'s scalings.
 """
 from __future__ import annotations
 
@@ -58,6 +60,34 @@ def skip_scaling(sigma, sigma_data=0.5, sigma_min=0.002):
     return sigma_data ** 2 / ((sigma - sigma_min) ** 2 + sigma_data ** 2)        # :211-230
 
 
+def output_scaling_train(sigma, sigma_data=0.5, sigma_min=0.002):
+    return (sigma_data * sigma) / (sigma_data ** 2 + sigma ** 2) ** 0.5           # :189-208 (training mode of ect_forward: no sigma_min)
+
+
+def skip_scaling_train(sigma, sigma_data=0.5, sigma_min=0.002):
+    return sigma_data ** 2 / (sigma ** 2 + sigma_data ** 2)                       # :233-252
+
+
+def t_to_r_sigmoid(k, b, q, t, stage):
+    """cm_generator.py:328-333: r = t (1 - q^-(stage+1) (1 + k sigmoid(-b t))), clamped at 0 (r = 0 wherever the bracket is negative:
+    with k = 8, b = 1, q = 2, stage 0 every t < ln 7)."""
+    adj = 1 + k * torch.sigmoid(-b * t)
+    decay = 1 / q ** (stage + 1)
+    ratio = 1 - decay * adj
+    return torch.clamp(t * ratio, min=0)
+
+
+FT_MODES = ("cm", "ect")
+
+
+def check_ft_mode(opt):
+    """alg_ddpm_ft_mode of `opt` ("cm" when the option is absent); anything the reference's parser would refuse raises"""
+    mode = getattr(opt, "alg_ddpm_ft_mode", "cm")
+    if mode not in FT_MODES:
+        raise NotImplementedError(f"alg_ddpm_ft_mode={mode!r}: one of {FT_MODES}")
+    return mode
+
+
 class NoiseLevelEmbedding(nn.Module):
     """cm_generator.py:255-280.  `projection.3` of the reference is a parameter-free Rearrange."""
 
@@ -93,8 +123,21 @@ class CMGenerator(nn.Module):
         self.current_t = 0
         self.arena = None
         self.act_dtype = torch.bfloat16
-        if getattr(opt, "alg_ddpm_ft_mode", "cm") != "cm":
-            raise NotImplementedError("alg_ddpm_ft_mode='ect' is not implemented (SURVEY.md 8: consistency-model branch only)")
+        self.ft_mode = check_ft_mode(opt)
+        # ECT (:315-326)
+        self.P_mean, self.P_std = -1.1, 2.0
+        self.q, self.k, self.b = 2.0, 8.0, 1.0
+        self.stage = 0
+        self.double_ticks = 1000
+        self.ratio = 1 - 1 / self.q ** (self.stage + 1)
+        self.t_to_r = t_to_r_sigmoid
+
+    def update_stage(self, cur_tick):
+        """:335-340: the stage doubles the t -> r ratio's denominator every `double_ticks` ticks and never goes back"""
+        new_stage = cur_tick // self.double_ticks
+        if new_stage > self.stage:
+            self.stage = new_stage
+            self.ratio = 1 - 1 / self.q ** (self.stage + 1)
 
     # ---- MI355X finalisation ---------------------------------------------------------------
     def jg_finalize(self, device, act_dtype=torch.bfloat16):
@@ -114,24 +157,10 @@ class CMGenerator(nn.Module):
     def _unet(self, xin, sigma):
         return self.cm_model(xin, self.embed_sigmas(sigma))
 
-    def forward_nhwc(self, x, total_training_steps=50000, mask=None, x_cond=None, noise=None, timesteps=None):
-        """The training forward with the two UNet outputs left in NHWC 16-bit.  Returns a dict with F_next (with
-        gradient), F_cur, the noisy inputs (fp32 NCHW), the four scalings, sigmas, loss weights, num_timesteps."""
-        if self.arena is None:
-            raise RuntimeError("CMGenerator.jg_finalize(device) has not been called")
-        if x.dim() != 4:
-            raise NotImplementedError("video (5-D) inputs are outside the SURVEY.md 8 hot path")
-        self.arena.ensure_fresh()
+    def _student_teacher(self, x, noise, next_sigmas, current_sigmas, mask, x_cond):
+        """the two UNet passes of one step: the student on x + next_sigmas eps (with gradient), the teacher on x + current_sigmas eps
+        (same weights, no gradient).  Returns (next_noisy_x, F_next, current_noisy_x, F_cur): noisy images fp32 NCHW, outputs NHWC 16-bit."""
         dev = x.device
-        num_timesteps = improved_timesteps_schedule(self.current_t, total_training_steps, self.initial_timesteps,
-                                                    self.final_timesteps)
-        sigmas = karras_schedule(num_timesteps, self.sigma_min, self.sigma_max, self.rho, dev)
-        if noise is None:
-            noise = torch.randn_like(x)
-        if timesteps is None:
-            timesteps = lognormal_timestep_distribution(x.shape[0], sigmas, self.lognormal_mean, self.lognormal_std)
-        noise, timesteps = noise.to(dev), timesteps.to(dev)
-        current_sigmas, next_sigmas = sigmas[timesteps], sigmas[timesteps + 1]
         cpad = (x.shape[1] + (0 if x_cond is None else x_cond.shape[1]) + 7) // 8 * 8
         next_noisy_x, xin_next = ops.cm_noisy(x, noise, next_sigmas, mask, x_cond, self.act_dtype, cpad)
         if CM_FORK and x.is_cuda:
@@ -157,6 +186,43 @@ class CMGenerator(nn.Module):
             with torch.no_grad():
                 current_noisy_x, xin_cur = ops.cm_noisy(x, noise, current_sigmas, mask, x_cond, self.act_dtype, cpad)
                 F_cur = self._unet(xin_cur, current_sigmas)
+        return next_noisy_x, F_next, current_noisy_x, F_cur
+
+    def forward_nhwc(self, x, total_training_steps=50000, mask=None, x_cond=None, noise=None, timesteps=None, rnd_normal=None):
+        """The training forward with the two UNet outputs left in NHWC 16-bit.  Returns a dict with F_next (with
+        gradient), F_cur, the noisy inputs (fp32 NCHW), the four scalings, sigmas, loss weights, num_timesteps.
+        ft_mode "ect" (:396-442): F_next / F_cur are the passes at t / r, the noisy inputs are t_noisy_x / r_noisy_x, the scalings are
+        those of ect_forward (:342-365), and t, r [B] take the place of the schedule entries.  Injectable draws: (noise, rnd_normal)."""
+        if self.arena is None:
+            raise RuntimeError("CMGenerator.jg_finalize(device) has not been called")
+        if x.dim() != 4:
+            raise NotImplementedError("video (5-D) inputs are outside the SURVEY.md 8 hot path")
+        self.arena.ensure_fresh()
+        dev = x.device
+        if self.ft_mode == "ect":
+            if rnd_normal is None:                      # the reference's order: randn(B), then randn_like(x)
+                rnd_normal = torch.randn(x.shape[0], device=dev)
+            if noise is None:
+                noise = torch.randn_like(x)
+            noise, rnd_normal = noise.to(dev), rnd_normal.to(dev).float()
+            t = (rnd_normal * self.P_std + self.P_mean).exp()
+            r = self.t_to_r(self.k, self.b, self.q, t, self.stage)
+            t_noisy_x, F_next, r_noisy_x, F_cur = self._student_teacher(x, noise, t, r, mask, x_cond)
+            self.current_t += x.shape[0]
+            cs, co = (skip_scaling_train, output_scaling_train) if self.training else (skip_scaling, output_scaling)
+            return dict(F_next=F_next, F_cur=F_cur, t_noisy_x=t_noisy_x, r_noisy_x=r_noisy_x,
+                        cs_n=cs(t, self.sigma_data, self.sigma_min), co_n=co(t, self.sigma_data, self.sigma_min),
+                        cs_c=cs(r, self.sigma_data, self.sigma_min), co_c=co(r, self.sigma_data, self.sigma_min), t=t, r=r)
+        num_timesteps = improved_timesteps_schedule(self.current_t, total_training_steps, self.initial_timesteps,
+                                                    self.final_timesteps)
+        sigmas = karras_schedule(num_timesteps, self.sigma_min, self.sigma_max, self.rho, dev)
+        if noise is None:
+            noise = torch.randn_like(x)
+        if timesteps is None:
+            timesteps = lognormal_timestep_distribution(x.shape[0], sigmas, self.lognormal_mean, self.lognormal_std)
+        noise, timesteps = noise.to(dev), timesteps.to(dev)
+        current_sigmas, next_sigmas = sigmas[timesteps], sigmas[timesteps + 1]
+        next_noisy_x, F_next, current_noisy_x, F_cur = self._student_teacher(x, noise, next_sigmas, current_sigmas, mask, x_cond)
         self.current_t += x.shape[0]
         return dict(F_next=F_next, F_cur=F_cur, next_noisy_x=next_noisy_x, current_noisy_x=current_noisy_x,
                     cs_n=skip_scaling(next_sigmas, self.sigma_data, self.sigma_min),
@@ -203,11 +269,16 @@ class CMGenerator(nn.Module):
                 x = x * mf + (1 - mf) * y
         return x
 
-    def forward(self, x, total_training_steps=50000, mask=None, x_cond=None, noise=None, timesteps=None):
-        """reference :388-502 signature (plus the two injectable random draws); returns the reference's 7-tuple
-        (next_x, current_x, num_timesteps, sigmas, loss_weights, next_noisy_x, current_noisy_x) in NCHW fp32.
-        The tensors carry no autograd graph: training goes through forward_nhwc + ops.cm_loss."""
-        r = self.forward_nhwc(x, total_training_steps, mask, x_cond, noise, timesteps)
+    def forward(self, x, total_training_steps=50000, mask=None, x_cond=None, noise=None, timesteps=None, rnd_normal=None):
+        """reference :388-502 signature (plus the injectable random draws); returns the reference's 7-tuple
+        (next_x, current_x, num_timesteps, sigmas, loss_weights, next_noisy_x, current_noisy_x) in NCHW fp32, in ft_mode "ect" its
+        6-tuple (D_yt, D_yr, t_noisy_x, r_noisy_x, t, r).
+        The tensors carry no autograd graph: training goes through forward_nhwc + ops.cm_loss / ops.ect_loss."""
+        r = self.forward_nhwc(x, total_training_steps, mask, x_cond, noise, timesteps, rnd_normal)
+        if self.ft_mode == "ect":
+            D_yt = ops.cm_combine(r["t_noisy_x"], r["F_next"].detach(), r["cs_n"], r["co_n"])
+            D_yr = ops.cm_combine(r["r_noisy_x"], r["F_cur"], r["cs_c"], r["co_c"])
+            return D_yt, D_yr, r["t_noisy_x"], r["r_noisy_x"], r["t"], r["r"]
         next_x = ops.cm_combine(r["next_noisy_x"], r["F_next"].detach(), r["cs_n"], r["co_n"])
         current_x = ops.cm_combine(r["current_noisy_x"], r["F_cur"], r["cs_c"], r["co_c"])
         return next_x, current_x, r["num_timesteps"], r["sigmas"], r["loss_weights"], r["next_noisy_x"], r["current_noisy_x"]

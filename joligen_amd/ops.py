@@ -1698,6 +1698,64 @@ def cm_loss(F_next, F_cur, noisy_next, noisy_cur, cs_n, co_n, cs_c, co_c, mask, 
                            chub, float(lam), float(grad_scale))
 
 
+ECT_C = 1e-6                 # CMModel.c (cm_model.py:120)
+_ECT_MAX_BLOCKS = 64         # per-sample partial sums of jg_ect_loss (csrc/elementwise.hip)
+
+
+def _ect_loss_launch(Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, dt, lam, grad_scale):
+    """(loss, dFn) of jg_ect_loss; every argument already contiguous / fp32 / int64 as the kernel reads it"""
+    B, Cc, H, W = noisy_n.shape
+    for name, t, dtype in (("F_cur", Fc, Fn.dtype), ("noisy_next", noisy_n, torch.float32), ("noisy_cur", noisy_c, torch.float32)):
+        if t.dtype != dtype or not t.is_contiguous():
+            raise TypeError(f"ect_loss: {name} must be contiguous {dtype}, got {t.dtype}")
+    if tuple(Fn.shape[:3]) != (B, H, W) or Fc.shape != Fn.shape or noisy_c.shape != noisy_n.shape or not Fn.is_contiguous():
+        raise ValueError(f"ect_loss: F {tuple(Fn.shape)} / {tuple(Fc.shape)} against noisy {tuple(noisy_n.shape)} / {tuple(noisy_c.shape)}")
+    for v in (cs_n, co_n, cs_c, co_c, dt):
+        if v.numel() != B:
+            raise ValueError(f"ect_loss: per-sample vectors must hold {B} values, got {v.numel()}")
+    if mask is not None and mask.numel() != B * H * W:
+        raise ValueError(f"ect_loss: mask {tuple(mask.shape)} is not [B,1,H,W]")
+    loss = torch.empty((), device=Fn.device, dtype=torch.float32)
+    dFn = torch.empty_like(Fn)
+    nws = B * min((H * W + 255) // 256, _ECT_MAX_BLOCKS)
+    ws = torch.empty(nws, device=Fn.device, dtype=torch.float32)
+    check(_lib.lib().jg_ect_loss(_dt(Fn), Fn.data_ptr(), Fc.data_ptr(), noisy_n.data_ptr(), noisy_c.data_ptr(), cs_n.data_ptr(),
+                                 co_n.data_ptr(), cs_c.data_ptr(), co_c.data_ptr(), _p(mask), dt.data_ptr(), ws.data_ptr(), nws,
+                                 loss.data_ptr(), dFn.data_ptr(), B, Cc, H, W, Fn.shape[-1], ECT_C, lam, grad_scale, _st()), "jg_ect_loss")
+    return loss, dFn
+
+
+class _ECTLossFn(JGFunction):
+    @staticmethod
+    def forward(ctx, Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, dt, lam, grad_scale):
+        loss, dFn = _ect_loss_launch(Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, dt, lam, grad_scale)
+        ctx.save_for_backward(dFn)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        (dFn,) = ctx.saved_tensors
+        return (axpby(dFn, 1.0, alpha_dev=gout.contiguous().float()),) + (None,) * 11
+
+
+def ect_loss(F_next, F_cur, noisy_next, noisy_cur, cs_n, co_n, cs_c, co_c, mask, dt, lam=1.0, grad_scale=1.0):
+    """compute_ect_loss (cm_model.py:412-442, no perceptual terms) on the two UNet outputs (NHWC 16-bit): lam * mean_b of
+    (sqrt(sum_chw (m pred - m target)^2 + c^2) - c) / dt_b with dt = t - r; the gradient with respect to F_next comes out of the same
+    call (jg_ect_loss: two launches, no atomics) and is saved for the backward."""
+    _require_cuda(F_next, F_cur, noisy_next, noisy_cur, dt)
+    m = None
+    if mask is not None:
+        m = mask.contiguous()
+        if m.dtype != torch.int64:
+            m = m.long()
+    f = lambda t: t.reshape(-1).contiguous().float()
+    args = (F_next, F_cur.detach(), noisy_next, noisy_cur, f(cs_n), f(co_n), f(cs_c), f(co_c), m, f(dt), float(lam), float(grad_scale))
+    if TORCH_OPS_BOUNDARY:
+        return torch.ops.jg355.ect_loss(*args)[0]
+    return _ECTLossFn.apply(*args)
+
+
 class _ToNCHWFn(JGFunction):
     @staticmethod
     def forward(ctx, x, Cc):
@@ -2046,6 +2104,36 @@ def _op_lowres_roundtrip(x: torch.Tensor, hlo: int, wlo: int) -> torch.Tensor:
 @_op_lowres_roundtrip.register_fake
 def _(x, hlo, wlo):
     return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("jg355::ect_loss", mutates_args=())
+def _op_ect_loss(Fn: torch.Tensor, Fc: torch.Tensor, noisy_n: torch.Tensor, noisy_c: torch.Tensor, cs_n: torch.Tensor, co_n: torch.Tensor,
+                 cs_c: torch.Tensor, co_c: torch.Tensor, mask: Optional[torch.Tensor], dt: torch.Tensor, lam: float,
+                 grad_scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(easy-consistency-tuning loss, its gradient w.r.t. Fn times grad_scale) of compute_ect_loss (cm_model.py:412-442): jg_ect_loss"""
+    f = lambda t: t.reshape(-1).contiguous().float()
+    m = None if mask is None else mask.contiguous().long()
+    return _ect_loss_launch(Fn.contiguous(), Fc.contiguous(), noisy_n.contiguous(), noisy_c.contiguous(), f(cs_n), f(co_n), f(cs_c), f(co_c),
+                            m, f(dt), lam, grad_scale)
+
+
+@_op_ect_loss.register_fake
+def _(Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, dt, lam, grad_scale):
+    return Fn.new_empty((), dtype=torch.float32), torch.empty_like(Fn, memory_format=torch.contiguous_format)
+
+
+def _ect_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _ect_backward(ctx, gloss, gdFn):
+    (dFn,) = ctx.saved_tensors
+    g = None if gloss is None else axpby(dFn, 1.0, alpha_dev=gloss.contiguous().float())
+    return (g,) + (None,) * 11
+
+
+_op_ect_loss.register_autograd(_ect_backward, setup_context=_ect_setup)
 
 
 @torch.library.custom_op("jg355::ddpm_mse_loss", mutates_args=())
