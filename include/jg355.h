@@ -607,6 +607,22 @@ int jg_ect_loss(int dtype, const void* Fn, const void* Fc, const float* noisy_n,
                 const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask, const float* dt, float* ws,
                 int64_t ws_floats, float* loss, void* dFn, int B, int C, int H, int W, int Cpad, float c, float lambda,
                 float grad_scale, jg_stream_t s);
+/* Pixel loss between two 16-bit NHWC images (the supervised and identity L1 / MSE terms of models/cut_model.py:771-786).
+ *   x [S*M, H, W, Cpad] in S (1 or 2) segments of M images, each compared with the same y [M, H, W, Cpad] over the C valid channels;
+ *   segment s has a mode (0 off, 1 L1, 2 MSE) and a weight:  loss[s] = lambda_s * mean_{m,c,h,w}(|d| or d^2), d = x - y in fp32;
+ *   an off segment yields exactly 0.  The pad channels may hold anything (NaN included).
+ *   jg_pixel_loss     : two launches on `s`: per-block partial sums into `ws`, then each segment's partials added in index order.  No
+ *                       atomics, nothing to zero: the same bits on every run.  `ws` is the caller's, at least
+ *                       S * min(ceil(M*H*W / 256), 256) floats (`ws_floats` says how many it holds).
+ *   jg_pixel_loss_bwd : dx = g[s] * lambda_s / (M*C*H*W) * (sign(d) | 2 d), d recomputed, g a DEVICE vector of S upstream gradients
+ *                       (no host read: capturable); formed in fp32, rounded once; 0 in the pad channels, where d == 0 under L1 and
+ *                       everywhere in an off segment.
+ *   Cpad must be 8 (one 16-byte access per pixel; JG_ERR_UNSUPPORTED otherwise); x, y, dx 16-byte aligned, S in 1..2 and the modes in
+ *   0..2 (JG_ERR_BAD_ARG otherwise). */
+int jg_pixel_loss(int dtype, const void* x, const void* y, float* ws, int64_t ws_floats, float* loss, int S, int M, int C, int H, int W,
+                  int Cpad, int mode0, int mode1, float lambda0, float lambda1, jg_stream_t s);
+int jg_pixel_loss_bwd(int dtype, const void* x, const void* y, const float* g, void* dx, int S, int M, int C, int H, int W, int Cpad,
+                      int mode0, int mode1, float lambda0, float lambda1, jg_stream_t s);
 int jg_noise_level_embedding(const float* sigma, const float* W, float* emb, int Bn, int half, jg_stream_t s);
 /* gradient of the embedding with respect to W, ACCUMULATED into dW (the reference trains W: set_requires_grad(net, True),
  * base_model.py:1196-1217) */

@@ -932,6 +932,85 @@ __global__ __launch_bounds__(256) void ect_grad_kernel(const T* __restrict__ Fn,
   }
 }
 
+// Pixel loss between two 16-bit NHWC images (cut_model.py:771-786: nn.L1Loss / nn.MSELoss of the supervised and identity terms).
+//   x [S*M, H, W, 8] in S segments of M images, every segment compared with the same y [M, H, W, 8]; per segment a mode (0 off, 1 L1,
+//   2 MSE) and a weight:  loss_s = lambda_s * mean_{m,c,h,w} (|d| or d^2),  d = x - y in fp32 over the C valid channels.
+// Forward = two kernels on one stream: pixel_partial_kernel leaves one partial sum per block in the caller's workspace (every slot
+// written, also by an off segment: nothing to zero), pixel_final_kernel adds each segment's partials in index order.  No atomics: the same
+// bits on every run.  grid = (blocks per segment, S); one pixel per thread and trip, one 16-byte load of each image.  The pad channels
+// arrive with the pixel's load and are never selected.
+// Backward (pixel_grad_kernel): dx = g_s * lambda_s / N * (sign(d) | 2 d) with d recomputed and g_s read on the device, the product formed
+// in fp32 and rounded once; one 16-byte store per pixel, zeros in the pad channels and in an off segment.
+constexpr int PIXEL_MAX_BLOCKS = 256;   // per segment; the workspace holds S * PIXEL_MAX_BLOCKS floats at most
+
+template <typename T>
+__global__ __launch_bounds__(256) void pixel_partial_kernel(const T* __restrict__ x, const T* __restrict__ y, float* __restrict__ partial,
+                                                            int mode0, int mode1, int C, long MP) {
+  __shared__ float s_part[4];
+  const int s = blockIdx.y;
+  const int mode = s ? mode1 : mode0;
+  float acc = 0.f;
+  if (mode != 0) {
+    const uint4* xs = reinterpret_cast<const uint4*>(x) + (long)s * MP;
+#pragma unroll 2
+    for (long p = blockIdx.x * 256L + threadIdx.x; p < MP; p += gridDim.x * 256L) {
+      float fx[8], fy[8];
+      unpack8<T>(xs[p], fx);
+      unpack8<T>(reinterpret_cast<const uint4*>(y)[p], fy);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        if (c < C) {
+          const float d = fx[c] - fy[c];
+          acc = mode == 1 ? acc + fabsf(d) : fmaf(d, d, acc);
+        }
+      }
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[(long)s * gridDim.x + blockIdx.x] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+}
+
+__global__ void pixel_final_kernel(const float* __restrict__ partial, float* __restrict__ loss, int S, int nblk, int mode0, int mode1,
+                                   float lambda0, float lambda1, float invN) {
+  const int s = threadIdx.x;
+  if (s >= S) return;
+  float sum = 0.f;
+  for (int k = 0; k < nblk; ++k) sum += partial[(long)s * nblk + k];
+  loss[s] = (s ? mode1 : mode0) != 0 ? (s ? lambda1 : lambda0) * (sum * invN) : 0.f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pixel_grad_kernel(const T* __restrict__ x, const T* __restrict__ y, const float* __restrict__ g,
+                                                         T* __restrict__ dx, int S, int mode0, int mode1, float lambda0, float lambda1,
+                                                         float invN, int C, long MP) {
+  const float coef0 = mode0 != 0 ? g[0] * lambda0 * invN : 0.f;
+  const float coef1 = S > 1 && mode1 != 0 ? g[1] * lambda1 * invN : 0.f;
+  const long total = (long)S * MP;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+    const bool second = i >= MP;
+    const int mode = second ? mode1 : mode0;
+    const float coef = second ? coef1 : coef0;
+    float fx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (mode != 0) {
+      float fy[8];
+      unpack8<T>(reinterpret_cast<const uint4*>(x)[i], fx);
+      unpack8<T>(reinterpret_cast<const uint4*>(y)[second ? i - MP : i], fy);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        float gout = 0.f;
+        if (c < C) {
+          const float d = fx[c] - fy[c];
+          gout = mode == 1 ? (d > 0.f ? coef : d < 0.f ? -coef : 0.f) : coef * (2.0f * d);
+        }
+        fx[c] = gout;
+      }
+    }
+    reinterpret_cast<uint4*>(dx)[i] = pack8<T>(fx);
+  }
+}
+
 // NoiseLevelEmbedding (cm_generator.py:276-280): h = sigma * W * 2 * pi; [sin(h) | cos(h)]
 __global__ void noise_level_embedding_kernel(const float* __restrict__ sigma, const float* __restrict__ W, float* __restrict__ emb,
                                              int Bn, int half) {
@@ -1161,6 +1240,41 @@ extern "C" int jg_ect_loss(int dtype, const void* Fn, const void* Fc, const floa
                     hipLaunchKernelGGL((ect_grad_kernel<T>), dim3(nblk, B), dim3(256), 0, (hipStream_t)s, (const T*)Fn, (const T*)Fc,
                                        noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, dt, ws, loss, (T*)dFn, B, C, HW, c, lambda,
                                        grad_scale););
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+static int pixel_loss_args(const void* x, const void* y, int S, int M, int C, int H, int W, int Cpad, int mode0, int mode1) {
+  if (!x || !y || S < 1 || S > 2 || M < 1 || C < 1 || H < 1 || W < 1 || Cpad < C || mode0 < 0 || mode0 > 2 || mode1 < 0 || mode1 > 2)
+    return JG_ERR_BAD_ARG;
+  if (Cpad != 8) return JG_ERR_UNSUPPORTED;             // one 16-byte access per pixel is the whole channel vector
+  if (((uintptr_t)x | (uintptr_t)y) & 15) return JG_ERR_BAD_ARG;
+  return JG_OK;
+}
+extern "C" int jg_pixel_loss(int dtype, const void* x, const void* y, float* ws, int64_t ws_floats, float* loss, int S, int M, int C,
+                             int H, int W, int Cpad, int mode0, int mode1, float lambda0, float lambda1, jg_stream_t s) {
+  const int rc = pixel_loss_args(x, y, S, M, C, H, W, Cpad, mode0, mode1);
+  if (rc != JG_OK) return rc;
+  if (!ws || !loss) return JG_ERR_BAD_ARG;
+  const long MP = (long)M * H * W;
+  const long need = (MP + 255) / 256;
+  const int nblk = (int)(need < PIXEL_MAX_BLOCKS ? need : PIXEL_MAX_BLOCKS);
+  if (ws_floats < (long)S * nblk) return JG_ERR_BAD_ARG;
+  const float invN = (float)(1.0 / ((double)MP * C));
+  JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((pixel_partial_kernel<T>), dim3(nblk, S), dim3(256), 0, (hipStream_t)s, (const T*)x,
+                                              (const T*)y, ws, mode0, mode1, C, MP););
+  hipLaunchKernelGGL(pixel_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, ws, loss, S, nblk, mode0, mode1, lambda0, lambda1, invN);
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+extern "C" int jg_pixel_loss_bwd(int dtype, const void* x, const void* y, const float* g, void* dx, int S, int M, int C, int H, int W,
+                                 int Cpad, int mode0, int mode1, float lambda0, float lambda1, jg_stream_t s) {
+  const int rc = pixel_loss_args(x, y, S, M, C, H, W, Cpad, mode0, mode1);
+  if (rc != JG_OK) return rc;
+  if (!g || !dx || ((uintptr_t)dx & 15)) return JG_ERR_BAD_ARG;
+  const long MP = (long)M * H * W;
+  const float invN = (float)(1.0 / ((double)MP * C));
+  JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((pixel_grad_kernel<T>), dim3(grid_for(S * MP)), dim3(256), 0, (hipStream_t)s, (const T*)x,
+                                              (const T*)y, g, (T*)dx, S, mode0, mode1, lambda0, lambda1, invN, C, MP););
   JG_CHECK_LAUNCH();
   return JG_OK;
 }

@@ -2,8 +2,9 @@
 (`__init__` :216-503, `data_dependent_initialize` :505-548, `forward_cut` :611-688, `compute_G_loss_cut` :708-837,
 `calculate_feats` :848-887, `calculate_NCE_loss` :889-909) and models/base_gan_model.py (`compute_D_loss(_generic)`
 :341-419, `compute_G_loss_GAN(_generic)` :421-503) for the default configuration: G_netG='resnet', D_netDs=['basic'],
-alg_cut_netF='mlp_sample', alg_cut_nce_loss in {'monce', 'patchnce', 'SRC_hDCE'}, nce_idt, lsgan, no semantic / multimodal / context /
-temporal / augmentation branches.
+alg_cut_netF='mlp_sample', alg_cut_nce_loss in {'monce', 'patchnce', 'SRC_hDCE'}, nce_idt, lsgan, optionally the paired pixel loss
+(alg_cut_supervised_loss 'L1' / 'MSE') and the identity pixel loss (alg_cut_MSE_idt), no semantic / multimodal / context / temporal /
+augmentation branches.
 
 Per iteration (reference order): group G = {G_A, F}: fake = G(cat(real_A, real_B)); loss_G_tot = lambda_GAN * lsgan(D(fake_B), 1)
 + (NCE(real_A, fake_B) + NCE(real_B, idt_B)) / 2; backward; Adam step on G and on F (two fused launches).  Group D: fake from the
@@ -31,7 +32,7 @@ CUT_DEFAULTS = dict(
     alg_cut_lambda_NCE=1.0, alg_cut_lambda_SRC=0.0, alg_cut_nce_idt=True, alg_cut_nce_layers="0,4,8,12,16",
     alg_cut_nce_includes_all_negatives_from_minibatch=False, alg_cut_nce_loss="monce", alg_cut_netF="mlp_sample",
     alg_cut_netF_nc=256, alg_cut_nce_T=0.07, alg_cut_HDCE_gamma=1.0, alg_cut_HDCE_gamma_min=1.0, alg_cut_num_patches=256, alg_cut_flip_equivariance=False, alg_cut_MSE_idt=False,
-    alg_cut_supervised_loss=[""], alg_gan_lambda=1.0, train_gan_mode="lsgan", D_netDs=["basic"], D_ndf=64, D_n_layers=3,
+    alg_cut_supervised_loss=[""], alg_cut_lambda_supervised=1.0, alg_cut_lambda_MSE_idt=1.0, alg_gan_lambda=1.0, train_gan_mode="lsgan", D_netDs=["basic"], D_ndf=64, D_n_layers=3,
     D_dropout=False, D_spectral=False, dataaug_D_label_smooth=False, dataaug_D_noise=0.0, dataaug_APA=False,
     dataaug_D_diffusion=False, train_semantic_mask=False, train_semantic_cls=False, train_mask_out_mask=False,
 )
@@ -71,6 +72,37 @@ def check_nce_options(opt):
     return hdce
 
 
+def check_pixel_loss_options(opt):
+    """the pixel-loss options of cut_model.py:309-319 that this build accepts; returns the ops.pixel_loss modes (supervised term, identity
+    term).  "MSE" wins over "L1" when both are listed (the reference's if / elif); alg_cut_MSE_idt is an L1 loss despite its name (:309-310)
+    and is off at lambda_MSE_idt <= 0 (:771).  Host-only (no device)."""
+    for k in ("alg_cut_supervised_loss", "alg_cut_lambda_supervised", "alg_cut_MSE_idt", "alg_cut_lambda_MSE_idt", "alg_cut_nce_idt"):
+        if not hasattr(opt, k):
+            setattr(opt, k, CUT_DEFAULTS[k])
+    sup = [s for s in opt.alg_cut_supervised_loss if s]
+    bad = [s for s in sup if s not in ("L1", "MSE")]
+    if bad:
+        raise NotImplementedError(f"alg_cut_supervised_loss={bad!r}: 'L1' and 'MSE' are built ('LPIPS' / 'DISTS' need pretrained networks)")
+    if opt.alg_cut_MSE_idt and not opt.alg_cut_nce_idt:      # the reference reads an idt_B that forward_cut never made
+        raise ValueError("alg_cut_MSE_idt needs alg_cut_nce_idt: the identity image G(real_B) exists only with it")
+    mode_sup = ops.PIXEL_MSE if "MSE" in sup else ops.PIXEL_L1 if "L1" in sup else ops.PIXEL_OFF
+    mode_idt = ops.PIXEL_L1 if opt.alg_cut_MSE_idt and float(opt.alg_cut_lambda_MSE_idt) > 0.0 else ops.PIXEL_OFF
+    return mode_sup, mode_idt
+
+
+def cut_loss_names(opt, discriminators_names):
+    """loss_names of the generator group in the reference's order (cut_model.py:444-455): G_tot, G_NCE, [G_supervised], [G_NCE_Y], [G_MSE_idt],
+    G_GAN_*.  Host-only (no device)."""
+    names = ["G_tot", "G_NCE"]
+    if [s for s in getattr(opt, "alg_cut_supervised_loss", [""]) if s]:
+        names.append("G_supervised")
+    if getattr(opt, "alg_cut_nce_idt", True):
+        names.append("G_NCE_Y")
+    if getattr(opt, "alg_cut_MSE_idt", False):
+        names.append("G_MSE_idt")
+    return names + ["G_GAN_" + dn for dn in discriminators_names]
+
+
 class CUTModel(BaseModel):
     def __init__(self, opt, rank):
         for k, v in CUT_DEFAULTS.items():
@@ -94,13 +126,16 @@ class CUTModel(BaseModel):
         if opt.alg_cut_netF != "mlp_sample":
             raise NotImplementedError(f"alg_cut_netF={opt.alg_cut_netF!r}")
         self.hdce = check_nce_options(opt)
-        for flag in ("model_multimodal", "alg_cut_flip_equivariance", "alg_cut_MSE_idt", "train_semantic_mask", "train_semantic_cls",
+        self.pixel_modes = check_pixel_loss_options(opt)      # (supervised term, identity term) of ops.pixel_loss
+        for flag in ("model_multimodal", "alg_cut_flip_equivariance", "train_semantic_mask", "train_semantic_cls",
                      "train_mask_out_mask", "dataaug_APA", "dataaug_D_diffusion"):
             if getattr(opt, flag, False):
                 raise NotImplementedError(f"{flag} is outside the SURVEY.md 8 hot path")
-        if [s for s in opt.alg_cut_supervised_loss if s] or opt.dataaug_D_noise > 0:
-            raise NotImplementedError("supervised / noisy-D terms are outside the built path")
-        self.loss_G_SRC = 0.0      # cut_model.py:760: reset on every iteration without alg_cut_MSE_idt, never part of loss_G_tot
+        if opt.dataaug_D_noise > 0:
+            raise NotImplementedError("noisy-D terms are outside the built path")
+        self.loss_G_SRC = 0.0      # cut_model.py:734-761: computed there, never part of loss_G_tot; not computed here
+        # cut_model.py:752-766: with alg_cut_MSE_idt the identity contrastive term of SRC_hDCE runs with the hDCE weights too
+        self.hdce_idt_weighted = bool(self.hdce and opt.alg_cut_MSE_idt)
         # options that select ANOTHER network than the one built here must not be dropped silently: the generator /
         # PatchGAN below are the InstanceNorm, no-dropout, no-spectral-norm variants of gan_networks.define_G / define_D
         for name, built in (("G_dropout", False), ("D_dropout", False), ("D_spectral", False), ("G_spectral", False),
@@ -180,8 +215,7 @@ class CUTModel(BaseModel):
                                         backward_functions=["compute_D_loss"], loss_names_list=["loss_names_D"], optimizer=optD,
                                         loss_backward=["loss_D_tot"])
             self.networks_groups = [self.group_G, self.group_D]
-            self.loss_names_G = (["G_tot", "G_NCE", "G_NCE_Y"] if opt.alg_cut_nce_idt else ["G_tot", "G_NCE"]) + \
-                ["G_GAN_" + dn for dn in self.discriminators_names]
+            self.loss_names_G = cut_loss_names(opt, self.discriminators_names)
             self.loss_names_D = ["D_tot"] + ["D_GAN_" + dn for dn in self.discriminators_names]
             self.loss_names = self.loss_names_G + self.loss_names_D
             self.loss_functions_G = ["compute_G_loss_GAN", "compute_G_loss_cut"]
@@ -343,8 +377,9 @@ class CUTModel(BaseModel):
             n = B * Pl
             q = torch.cat([rows[i][0] for i in ls], dim=0)                           # [layer][term][B * P_l] problems
             k = torch.cat([rows[i][1] for i in ls], dim=0)
-            if self.hdce:      # problems [layer][term][B]: the NCE term (term 0) is weighted, the identity term is not (cut_model.py:734-766)
-                loss = ops.patch_hdce_loss(q, k, 2 * len(ls) * B, T, o.alg_cut_HDCE_gamma, 2 * B, B).view(len(ls), 2, n)
+            if self.hdce:      # problems [layer][term][B]: the NCE term (term 0) is weighted, the identity term only with alg_cut_MSE_idt (:734-766)
+                wperiod, wcount = (1, 1) if self.hdce_idt_weighted else (2 * B, B)
+                loss = ops.patch_hdce_loss(q, k, 2 * len(ls) * B, T, o.alg_cut_HDCE_gamma, wperiod, wcount).view(len(ls), 2, n)
             else:
                 loss = ops.patch_nce_loss(q, k, 2 * len(ls) * B, T, P, monce).view(len(ls), 2, n)
             return loss.mean(dim=2).sum(dim=0) * o.alg_cut_lambda_NCE
@@ -356,21 +391,43 @@ class CUTModel(BaseModel):
             tot = [tot[0] + m[0], tot[1] + m[1]]
         L = len(self.nce_layers)
         self.loss_G_NCE, self.loss_G_NCE_Y = tot[0] / L, tot[1] / L
-        self.loss_G_tot = self.loss_G_tot + (self.loss_G_NCE + self.loss_G_NCE_Y) * 0.5
+        self.loss_G_tot = self.loss_G_tot + (self.loss_G_NCE + self.loss_G_NCE_Y) * 0.5 + self._pixel_losses()
+
+    def _pixel_losses(self):
+        """cut_model.py:771-786,823-833: the supervised term lambda_supervised * L1 | MSE(fake_B, real_B) (aligned data) and the identity term
+        lambda_MSE_idt * L1(idt_B, real_B), both from ONE ops.pixel_loss call on `self.fake` = [fake_B | idt_B] (segment 0 / segment 1 against
+        the same real_B: no slices, one autograd node, one backward launch).  Sets loss_G_supervised / loss_G_MSE_idt (device tensors) and
+        returns their sum for loss_G_tot.  The reference adds the supervised term only if its value is > 0, a host read of a device scalar --
+        a synchronisation, and illegal inside the captured generator graph; the sum is added unconditionally here: a term that is 0 has a zero
+        gradient (sign(0) = 0, 2 * 0 = 0), so the update is the same.  With neither option set nothing is launched and 0 is returned."""
+        o = self.opt
+        mode_sup, mode_idt = self.pixel_modes
+        if mode_sup == ops.PIXEL_OFF and mode_idt == ops.PIXEL_OFF:
+            if o.alg_cut_MSE_idt:          # lambda_MSE_idt <= 0: the name is in loss_names, the value is 0
+                self.loss_G_MSE_idt = torch.zeros((), device=self.device)
+            return 0
+        modes, lambdas = (mode_sup, mode_idt), (o.alg_cut_lambda_supervised, o.alg_cut_lambda_MSE_idt)
+        S = 2 if o.alg_cut_nce_idt else 1
+        losses = ops.pixel_loss(self.fake, self.real_B, o.model_output_nc, modes[:S], lambdas[:S])
+        if mode_sup != ops.PIXEL_OFF:
+            self.loss_G_supervised = losses[0]
+        if o.alg_cut_MSE_idt:
+            self.loss_G_MSE_idt = losses[1]
+        return losses.sum()
 
     def compute_G_loss_cut(self):
-        """cut_model.py:708-837 (NCE + identity NCE)."""
+        """cut_model.py:708-837 (NCE + identity NCE + the supervised / identity pixel terms)."""
         if self._batched_nce():
             return self.compute_G_loss_cut_batched()
         fq, fk = self.calculate_feats(self.real_A, self.fake_B)
         self.loss_G_NCE = self.calculate_NCE_loss(fq, fk, weighted=True) if self.opt.alg_cut_lambda_NCE > 0.0 else 0.0
         if self.opt.alg_cut_nce_idt and self.opt.alg_cut_lambda_NCE > 0.0:
             fq, fk = self.calculate_feats(self.real_B, self.idt_B)
-            self.loss_G_NCE_Y = self.calculate_NCE_loss(fq, fk, weighted=False)
+            self.loss_G_NCE_Y = self.calculate_NCE_loss(fq, fk, weighted=self.hdce_idt_weighted)
             loss_NCE_both = (self.loss_G_NCE + self.loss_G_NCE_Y) * 0.5
         else:
             loss_NCE_both = self.loss_G_NCE
-        self.loss_G_tot = self.loss_G_tot + loss_NCE_both
+        self.loss_G_tot = self.loss_G_tot + loss_NCE_both + self._pixel_losses()
 
     def calculate_feats(self, src, tgt):
         """:848-887: q from the translated image, k from the source, SAME patch ids (drawn on the k pass)."""
@@ -388,7 +445,8 @@ class CUTModel(BaseModel):
         return feat_q_pool, feat_k_pool
 
     def calculate_NCE_loss(self, feat_q_pool, feat_k_pool, weighted=True):
-        """:889-909.  `weighted` (SRC_hDCE only): the NCE(G(X), X) term runs with the hDCE weights, the identity term with weight=None (:734-766)."""
+        """:889-909.  `weighted` (SRC_hDCE only): the NCE(G(X), X) term runs with the hDCE weights, the identity term with weight=None unless
+        alg_cut_MSE_idt is set (:734-766)."""
         total = 0.0
         for f_q, f_k, crit in zip(feat_q_pool, feat_k_pool, self.criterionNCE):
             loss = crit(feat_q=f_q, feat_k=f_k, current_batch=self.get_current_batch_size(), weighted=weighted) * self.opt.alg_cut_lambda_NCE

@@ -250,6 +250,7 @@ class CUTStepDriver:
                 m._forward_core()
                 m.compute_G_loss()
             names = ["fake", "fake_B", "loss_G_tot", "loss_G_NCE"] + ["loss_G_GAN_" + dn for dn in m.discriminators_names]
+            names += [k for k in ("loss_G_supervised", "loss_G_MSE_idt") if k[len("loss_"):] in m.loss_names_G]      # the pixel terms that exist
             st.outs = {k: getattr(m, k) for k in names + (["idt_B", "loss_G_NCE_Y"] if m.opt.alg_cut_nce_idt else [])}
             with torch.cuda.graph(st.bwd, pool=st.fwd.pool(), capture_error_mode="thread_local"):
                 ops.zero_pool_reset(m.device, True)

@@ -1756,6 +1756,76 @@ def ect_loss(F_next, F_cur, noisy_next, noisy_cur, cs_n, co_n, cs_c, co_c, mask,
     return _ECTLossFn.apply(*args)
 
 
+PIXEL_OFF, PIXEL_L1, PIXEL_MSE = 0, 1, 2       # segment modes of jg_pixel_loss
+_PIXEL_MAX_BLOCKS = 256                        # per-segment partial sums of jg_pixel_loss (csrc/elementwise.hip)
+
+
+def _pixel_loss_check(x, y, C, modes, lambdas):
+    """the argument checks of jg_pixel_loss / jg_pixel_loss_bwd, before any launch; returns (S, M, H, W, modes and lambdas padded to two)"""
+    S = len(modes)
+    if S not in (1, 2) or len(lambdas) != S or any(int(m) not in (PIXEL_OFF, PIXEL_L1, PIXEL_MSE) for m in modes):
+        raise ValueError(f"pixel_loss: modes {list(modes)} / lambdas {list(lambdas)}: one or two segments, each mode 0 (off), 1 (L1) or 2 (MSE)")
+    if x.dim() != 4 or y.dim() != 4:
+        raise ValueError(f"pixel_loss: x {tuple(x.shape)} / y {tuple(y.shape)} are not NHWC images")
+    if x.dtype not in _DT or y.dtype != x.dtype or not x.is_contiguous() or not y.is_contiguous():
+        raise TypeError(f"pixel_loss: x and y must be contiguous and of one 16-bit dtype, got {x.dtype} / {y.dtype}")
+    M, H, W, cpad = y.shape
+    if x.shape[0] != S * M or tuple(x.shape[1:]) != (H, W, cpad) or not 1 <= int(C) <= cpad:
+        raise ValueError(f"pixel_loss: x {tuple(x.shape)} is not {S} segment(s) of y {tuple(y.shape)} with {C} valid channels")
+    return S, M, H, W, [int(m) for m in modes] + [PIXEL_OFF] * (2 - S), [float(v) for v in lambdas] + [0.0] * (2 - S)
+
+
+def _pixel_loss_launch(x, y, C, modes, lambdas):
+    """the S losses of jg_pixel_loss (fp32 [S])"""
+    _require_cuda(x, y)
+    S, M, H, W, md, lam = _pixel_loss_check(x, y, C, modes, lambdas)
+    loss = torch.empty(S, device=x.device, dtype=torch.float32)
+    nws = S * min((M * H * W + 255) // 256, _PIXEL_MAX_BLOCKS)
+    ws = torch.empty(nws, device=x.device, dtype=torch.float32)
+    check(_lib.lib().jg_pixel_loss(_dt(x), x.data_ptr(), y.data_ptr(), ws.data_ptr(), nws, loss.data_ptr(), S, M, int(C), H, W, x.shape[-1],
+                                   md[0], md[1], lam[0], lam[1], _st()), "jg_pixel_loss")
+    return loss
+
+
+def _pixel_loss_bwd_launch(x, y, g, C, modes, lambdas):
+    """d (sum_s g[s] loss[s]) / dx of jg_pixel_loss_bwd; g: the S upstream gradients, read on the device"""
+    _require_cuda(x, y, g)
+    S, M, H, W, md, lam = _pixel_loss_check(x, y, C, modes, lambdas)
+    if g.numel() != S:
+        raise ValueError(f"pixel_loss: the upstream gradient must hold {S} values, got {g.numel()}")
+    g = g.reshape(-1).contiguous().float()
+    dx = torch.empty_like(x)
+    check(_lib.lib().jg_pixel_loss_bwd(_dt(x), x.data_ptr(), y.data_ptr(), g.data_ptr(), dx.data_ptr(), S, M, int(C), H, W, x.shape[-1],
+                                       md[0], md[1], lam[0], lam[1], _st()), "jg_pixel_loss_bwd")
+    return dx
+
+
+class _PixelLossFn(JGFunction):
+    @staticmethod
+    def forward(ctx, x, y, C, modes, lambdas):
+        loss = _pixel_loss_launch(x, y, C, modes, lambdas)
+        ctx.save_for_backward(x, y)
+        ctx.cfg = (C, modes, lambdas)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, y = ctx.saved_tensors
+        return _pixel_loss_bwd_launch(x, y, gout, *ctx.cfg), None, None, None, None
+
+
+def pixel_loss(x, y, C, modes, lambdas):
+    """nn.L1Loss / nn.MSELoss between two 16-bit NHWC images over the C valid channels (cut_model.py:771-786): x [S*M, H, W, 8] in
+    S = len(modes) segments of M images, each compared with the same y [M, H, W, 8]; modes[s] in (PIXEL_OFF, PIXEL_L1, PIXEL_MSE).
+    Returns the S weighted losses lambdas[s] * mean (fp32 [S]; exactly 0 for an off segment).  The backward is ONE launch for all
+    segments: d = x - y is recomputed and the S upstream gradients are read on the device (jg_pixel_loss_bwd); y receives no gradient."""
+    modes, lambdas = tuple(int(m) for m in modes), tuple(float(v) for v in lambdas)
+    if TORCH_OPS_BOUNDARY:
+        return torch.ops.jg355.pixel_loss(x, y.detach(), int(C), list(modes), list(lambdas))
+    return _PixelLossFn.apply(x, y.detach(), int(C), modes, lambdas)
+
+
 class _ToNCHWFn(JGFunction):
     @staticmethod
     def forward(ctx, x, Cc):

@@ -16,13 +16,14 @@ tests/test_gpu_5_cutloss.py::test_cut_step_through_torch_ops holds the two forms
   act / act_bwd                              stand-alone ReLU / LeakyReLU / Tanh
   gather_patches / scatter_patches, l2_normalize / _bwd, patch_nce / patch_nce_bwd      PatchSampleF + PatchNCE / MoNCE (Sinkhorn inside)
   patch_hdce / patch_hdce_bwd                SRC_hDCE: weights from the key Gram matrix + weighted contrastive loss, one fused kernel
+  pixel_loss / pixel_loss_bwd                paired (supervised) and identity L1 / MSE between 16-bit images, both terms in one launch set
   gan_loss, hinge_loss                       GANLoss (lsgan / vanilla / wgangp) and the projected hinge; return (loss, d loss / d pred)
   spectral_weight / _bwd                     torch.nn.utils.spectral_norm: one power iteration, W / sigma; gradient through 1 / sigma
   bilinear2 / bilinear2_bwd                  F.interpolate(mode="bilinear", align_corners=...)
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -649,6 +650,44 @@ def _hdce_backward(ctx, dloss, *unused):
 
 
 patch_hdce.register_autograd(_hdce_backward, setup_context=_hdce_setup)
+
+
+# ---- paired / identity pixel losses ---------------------------------------------------------------------------------------------------
+@op("jg355::pixel_loss", mutates_args=())
+def pixel_loss(x: T, y: T, C: int, modes: List[int], lambdas: List[float]) -> T:
+    """nn.L1Loss / nn.MSELoss between 16-bit NHWC images (cut_model.py:771-786): x [S*M, H, W, 8] in S = len(modes) segments, each against
+    y [M, H, W, 8] over the C valid channels; mode 0 off, 1 L1, 2 MSE -> the S weighted losses (fp32 [S])"""
+    return ops._pixel_loss_launch(x.contiguous(), y.contiguous(), C, modes, lambdas)
+
+
+@pixel_loss.register_fake
+def _(x, y, C, modes, lambdas):
+    return x.new_empty((len(modes),), dtype=torch.float32)
+
+
+@op("jg355::pixel_loss_bwd", mutates_args=())
+def pixel_loss_bwd(x: T, y: T, g: T, C: int, modes: List[int], lambdas: List[float]) -> T:
+    """d (sum_s g[s] loss[s]) / dx: g [S] read on the device, d = x - y recomputed; zero pad channels / off segments"""
+    return ops._pixel_loss_bwd_launch(x.contiguous(), y.contiguous(), g, C, modes, lambdas)
+
+
+@pixel_loss_bwd.register_fake
+def _(x, y, g, C, modes, lambdas):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+def _pl_setup(ctx, inputs, output):
+    x, y, C, modes, lambdas = inputs
+    ctx.save_for_backward(x, y)
+    ctx.cfg = (C, list(modes), list(lambdas))
+
+
+def _pl_backward(ctx, g):
+    x, y = ctx.saved_tensors
+    return torch.ops.jg355.pixel_loss_bwd(x, y, g, *ctx.cfg), None, None, None, None
+
+
+pixel_loss.register_autograd(_pl_backward, setup_context=_pl_setup)
 
 
 # ---- GAN objectives: (loss, d loss / d pred) -------------------------------------------------------------------------------------------------
