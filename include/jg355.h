@@ -603,6 +603,21 @@ int jg_cm_combine(int dtype, const float* noisy, const void* F, const float* csk
 int jg_cm_loss(int dtype, const void* Fn, const void* Fc, const float* noisy_n, const float* noisy_c, const float* cs_n,
                const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask, const float* w, float* loss,
                void* dFn, int B, int C, int H, int W, int Cpad, float c_huber, float lambda, float grad_scale, jg_stream_t s);
+/* cm_gan (consistency training with discriminators): jg_cm_loss's pass that also writes the student's prediction.
+ *   jg_cm_gan_head     : loss (accumulates: zero it) and dFn exactly as jg_cm_loss computes them (the same per-element arithmetic and
+ *                        summation order), plus pred [B,H,W,8] = cs_n*noisy_n + co_n*Fn on the C valid channels, 0 in the pad channels,
+ *                        in the activation dtype: the discriminators' input.  One launch; one workgroup under JG_DETERMINISTIC=1,
+ *                        otherwise one atomic per workgroup.
+ *   jg_cm_gan_head_bwd : dF = g_loss[0] * dFn_cm + co_n[b] * dpred on the valid channels, 0 in the pad channels; g_loss a DEVICE scalar
+ *                        (no host read: capturable), dpred the 16-bit NHWC gradient of pred, or NULL (no GAN branch: g_loss * dFn_cm).
+ *   Cpad must be 8 (one 16-byte access per pixel; JG_ERR_UNSUPPORTED otherwise); Fn, Fc, dFn, pred, dFn_cm, dpred, dF 16-byte aligned
+ *   (JG_ERR_BAD_ARG otherwise). */
+int jg_cm_gan_head(int dtype, const void* Fn, const void* Fc, const float* noisy_n, const float* noisy_c, const float* cs_n,
+                   const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask, const float* w, float* loss,
+                   void* dFn, void* pred, int B, int C, int H, int W, int Cpad, float c_huber, float lambda, float grad_scale,
+                   jg_stream_t s);
+int jg_cm_gan_head_bwd(int dtype, const void* dFn_cm, const void* dpred, const float* g_loss, const float* co_n, void* dF, int B, int C,
+                       int H, int W, int Cpad, jg_stream_t s);
 int jg_ect_loss(int dtype, const void* Fn, const void* Fc, const float* noisy_n, const float* noisy_c, const float* cs_n,
                 const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask, const float* dt, float* ws,
                 int64_t ws_floats, float* loss, void* dFn, int B, int C, int H, int W, int Cpad, float c, float lambda,

@@ -187,6 +187,8 @@ SIGNATURES = {
     "jg_cm_combine": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
     "jg_cm_loss": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32,
                    c_f32, c_f32, c_f32, c_p],
+    "jg_cm_gan_head": [c_i32] + [c_p] * 13 + [c_i32] * 5 + [c_f32] * 3 + [c_p],
+    "jg_cm_gan_head_bwd": [c_i32] + [c_p] * 5 + [c_i32] * 5 + [c_p],
     "jg_ect_loss": [c_i32] + [c_p] * 11 + [c_i64, c_p, c_p] + [c_i32] * 5 + [c_f32] * 3 + [c_p],
     "jg_pixel_loss": [c_i32, c_p, c_p, c_p, c_i64, c_p] + [c_i32] * 8 + [c_f32, c_f32, c_p],
     "jg_pixel_loss_bwd": [c_i32, c_p, c_p, c_p, c_p] + [c_i32] * 8 + [c_f32, c_f32, c_p],

@@ -787,6 +787,23 @@ __global__ void cm_combine_kernel(const float* __restrict__ noisy, const T* __re
 //   pred = cs_n*noisy_n + co_n*F_n (student),  target = cs_c*noisy_c + co_c*F_c (no-grad teacher),
 //   loss = lambda * mean( w[b] * (sqrt((m*pred - m*target)^2 + c^2) - c) ),  m = the label mask AS IS (not clamped)
 //   dF_n = grad_scale * lambda * w[b]/N * d/sqrt(d^2+c^2) * m * co_n
+// one element of it, shared with cm_gan_head_kernel: adds w * (sqrt(d^2 + c^2) - c) to acc, returns dF_n ALREADY in the activation dtype
+// (the compiler folds the last product into the conversion, one rounding for fp16: the conversion belongs to the shared arithmetic) and
+// hands out the student's prediction (the discriminators' input of cm_gan)
+template <typename T>
+__device__ __forceinline__ T cm_elem(float csn, float xn, float con, float fn, float csc, float xc, float coc, float fc, float m, float wb,
+                                     float chub, float grad_scale, float lambda, float invN, float& acc, float& pred_out) {
+  // the sums are written as the fused multiply-adds the compiler has always formed for cm_loss_kernel: left to its choice, it contracts
+  // the other product first where F arrives in a register of its own (cm_gan_head_kernel), and the two kernels differ in the last bit
+  const float pred = fmaf(csn, xn, con * fn);
+  const float targ = fmaf(csc, xc, coc * fc);
+  const float d = fmaf(m, pred, -(m * targ));
+  const float r = sqrtf(fmaf(d, d, chub * chub));
+  acc = fmaf(wb, r - chub, acc);
+  pred_out = pred;
+  return from_f32<T>(grad_scale * lambda * invN * wb * (d / r) * m * con);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cm_loss_kernel(const T* __restrict__ Fn, const T* __restrict__ Fc,
                                                       const float* __restrict__ noisy_n, const float* __restrict__ noisy_c,
@@ -805,23 +822,90 @@ __global__ __launch_bounds__(256) void cm_loss_kernel(const T* __restrict__ Fn, 
     const float m = mask ? (float)mask[i] : 1.0f;
     const float wb = w[b];
     for (int c = 0; c < Cpad; ++c) {
-      float gout = 0.f;
+      T gout = from_f32<T>(0.f);
       if (c < C) {
         const long q = ((long)b * C + c) * HW + p;
-        const float pred = cs_n[b] * noisy_n[q] + co_n[b] * to_f32(Fn[i * Cpad + c]);
-        const float targ = cs_c[b] * noisy_c[q] + co_c[b] * to_f32(Fc[i * Cpad + c]);
-        const float d = m * pred - m * targ;
-        const float r = sqrtf(d * d + chub * chub);
-        acc += wb * (r - chub);
-        gout = grad_scale * lambda * invN * wb * (d / r) * m * co_n[b];
+        float pred;
+        gout = cm_elem<T>(cs_n[b], noisy_n[q], co_n[b], to_f32(Fn[i * Cpad + c]), cs_c[b], noisy_c[q], co_c[b], to_f32(Fc[i * Cpad + c]), m,
+                          wb, chub, grad_scale, lambda, invN, acc, pred);
       }
-      if (dFn) dFn[i * Cpad + c] = from_f32<T>(gout);
+      if (dFn) dFn[i * Cpad + c] = gout;
     }
   }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(loss, (s_part[0] + s_part[1] + s_part[2] + s_part[3]) * invN * lambda);
+}
+
+// cm_gan (cm_gan_model.py: compute_cm_gan_loss = compute_cm_loss, then the GAN terms on fake_B = pred_x): cm_loss_kernel's loss and
+// gradient (cm_elem, the same pixel -> thread map and summation order: the same bits) plus the student's prediction
+//   pred[b,p,c] = cs_n*noisy_n + co_n*F_n   in the activation dtype, NHWC, zeros in the pad channels: what the discriminators read.
+// One pixel per thread and trip: one 16-byte load of each UNet output, the fp32 NCHW planes read along the pixel index, one 16-byte store
+// each of dFn and pred.  96 B per pixel at C = 3 (2 x 16 + 6 x 4 + 8 mask + 2 x 16); no LDS beyond the four wave partials.
+template <typename T>
+__global__ __launch_bounds__(256) void cm_gan_head_kernel(const T* __restrict__ Fn, const T* __restrict__ Fc,
+                                                          const float* __restrict__ noisy_n, const float* __restrict__ noisy_c,
+                                                          const float* __restrict__ cs_n, const float* __restrict__ co_n,
+                                                          const float* __restrict__ cs_c, const float* __restrict__ co_c,
+                                                          const int64_t* __restrict__ mask, const float* __restrict__ w,
+                                                          float* __restrict__ loss, T* __restrict__ dFn, T* __restrict__ pred_nhwc,
+                                                          int B, int C, long HW, float chub, float lambda, float grad_scale) {
+  __shared__ float s_part[4];
+  const long total = (long)B * HW;
+  const float invN = 1.0f / ((float)total * (float)C);
+  float acc = 0.f;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+    const int b = i / HW;
+    const long p = i % HW;
+    const float m = mask ? (float)mask[i] : 1.0f;
+    const float wb = w[b], csn = cs_n[b], con = co_n[b], csc = cs_c[b], coc = co_c[b];
+    float fn[8], fc[8], pr[8];
+    unpack8<T>(reinterpret_cast<const uint4*>(Fn)[i], fn);
+    unpack8<T>(reinterpret_cast<const uint4*>(Fc)[i], fc);
+    uint32_t gw[4] = {0u, 0u, 0u, 0u};                     // the gradient's 8 x T, packed as cm_elem hands them out
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      float pred = 0.f;
+      if (c < C) {
+        const long q = ((long)b * C + c) * HW + p;
+        const T gout = cm_elem<T>(csn, noisy_n[q], con, fn[c], csc, noisy_c[q], coc, fc[c], m, wb, chub, grad_scale, lambda, invN, acc, pred);
+        gw[c >> 1] |= (uint32_t)to_bits<T>(gout) << ((c & 1) * 16);
+      }
+      pr[c] = pred;
+    }
+    reinterpret_cast<uint4*>(dFn)[i] = make_uint4(gw[0], gw[1], gw[2], gw[3]);
+    reinterpret_cast<uint4*>(pred_nhwc)[i] = pack8<T>(pr);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(loss, (s_part[0] + s_part[1] + s_part[2] + s_part[3]) * invN * lambda);
+}
+
+// its backward: dF_n = g * dFn_cm + co_n[b] * dpred on the C valid channels (g = d(loss_G_tot)/d(cm loss), a device scalar; dpred = the
+// gradient that came back through the discriminators), 0 in the pad channels; formed in fp32 and rounded once.  dpred == nullptr: no GAN
+// branch, g * dFn_cm as jg_axpby gives it.  One pixel per thread and trip, 16-byte accesses only.
+template <typename T>
+__global__ __launch_bounds__(256) void cm_gan_head_bwd_kernel(const T* __restrict__ dFn_cm, const T* __restrict__ dpred,
+                                                              const float* __restrict__ g_loss, const float* __restrict__ co_n,
+                                                              T* __restrict__ dF, int B, int C, long HW) {
+  const float g = *g_loss;
+  const long total = (long)B * HW;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+    float a[8], d[8];
+    unpack8<T>(reinterpret_cast<const uint4*>(dFn_cm)[i], a);
+    if (dpred) {
+      const float con = co_n[i / HW];
+      unpack8<T>(reinterpret_cast<const uint4*>(dpred)[i], d);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) a[c] = c < C ? g * a[c] + con * d[c] : 0.f;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) a[c] = c < C ? a[c] * g : 0.f;
+    }
+    reinterpret_cast<uint4*>(dF)[i] = pack8<T>(a);
+  }
 }
 
 // Easy-consistency-tuning loss with its gradient (compute_ect_loss, cm_model.py:412-442):
@@ -1219,6 +1303,33 @@ extern "C" int jg_cm_loss(int dtype, const void* Fn, const void* Fc, const float
   JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((cm_loss_kernel<T>), dim3(loss_grid(total, 256, 1024)), dim3(256), 0, (hipStream_t)s,
                                               (const T*)Fn, (const T*)Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, w, loss,
                                               (T*)dFn, B, C, H * W, Cpad, c_huber, lambda, grad_scale););
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+extern "C" int jg_cm_gan_head(int dtype, const void* Fn, const void* Fc, const float* noisy_n, const float* noisy_c,
+                              const float* cs_n, const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask,
+                              const float* w, float* loss, void* dFn, void* pred, int B, int C, int H, int W, int Cpad, float c_huber,
+                              float lambda, float grad_scale, jg_stream_t s) {
+  if (!Fn || !Fc || !noisy_n || !noisy_c || !cs_n || !co_n || !cs_c || !co_c || !w || !loss || !dFn || !pred || B < 1 || C < 1 ||
+      H < 1 || W < 1 || Cpad < C)
+    return JG_ERR_BAD_ARG;
+  if (Cpad != 8) return JG_ERR_UNSUPPORTED;             // one 16-byte access per pixel is the whole channel vector
+  if (((uintptr_t)Fn | (uintptr_t)Fc | (uintptr_t)dFn | (uintptr_t)pred) & 15) return JG_ERR_BAD_ARG;
+  const long HW = (long)H * W;
+  JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((cm_gan_head_kernel<T>), dim3(loss_grid(B * HW, 256, 1024)), dim3(256), 0, (hipStream_t)s,
+                                              (const T*)Fn, (const T*)Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, w, loss,
+                                              (T*)dFn, (T*)pred, B, C, HW, c_huber, lambda, grad_scale););
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+extern "C" int jg_cm_gan_head_bwd(int dtype, const void* dFn_cm, const void* dpred, const float* g_loss, const float* co_n, void* dF,
+                                  int B, int C, int H, int W, int Cpad, jg_stream_t s) {
+  if (!dFn_cm || !g_loss || !co_n || !dF || B < 1 || C < 1 || H < 1 || W < 1 || Cpad < C) return JG_ERR_BAD_ARG;
+  if (Cpad != 8) return JG_ERR_UNSUPPORTED;
+  if (((uintptr_t)dFn_cm | (uintptr_t)dpred | (uintptr_t)dF) & 15) return JG_ERR_BAD_ARG;
+  const long HW = (long)H * W;
+  JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((cm_gan_head_bwd_kernel<T>), dim3(grid_for(B * HW, 256, 2048)), dim3(256), 0,
+                                              (hipStream_t)s, (const T*)dFn_cm, (const T*)dpred, g_loss, co_n, (T*)dF, B, C, HW););
   JG_CHECK_LAUNCH();
   return JG_OK;
 }

@@ -11,6 +11,10 @@ def create_model(opt, rank):
         from .cm_model import CMModel
 
         return CMModel(opt, rank)
+    if opt.model_type == "cm_gan":
+        from .cm_gan_model import CMGanModel
+
+        return CMGanModel(opt, rank)
     if opt.model_type == "cut":
         from .cut_model import CUTModel
 

@@ -16,17 +16,15 @@ import warnings
 
 import torch
 
-from .._autograd import JGFunction
 from .. import ops
 from ..modules.NCE.hdce import PatchHDCELoss
 from ..modules.NCE.patchnce import MoNCELoss, PatchNCELoss
 from ..modules.cut_networks import PatchSampleF
-from ..modules.discriminators import NLayerDiscriminator
-from ..modules.loss import DiscriminatorGANLoss
 from ..modules.resnet_generator import ResnetGenerator
 from ..util.image_pool import ImagePool
 from .base_model import BaseModel, NetworkGroup
 from .cut_step import CUTStepDriver, gate
+from .gan_common import _ScaleGradFn, check_discriminator_options, define_D_optimizers, define_discriminators
 
 CUT_DEFAULTS = dict(
     alg_cut_lambda_NCE=1.0, alg_cut_lambda_SRC=0.0, alg_cut_nce_idt=True, alg_cut_nce_layers="0,4,8,12,16",
@@ -36,19 +34,6 @@ CUT_DEFAULTS = dict(
     D_dropout=False, D_spectral=False, dataaug_D_label_smooth=False, dataaug_D_noise=0.0, dataaug_APA=False,
     dataaug_D_diffusion=False, train_semantic_mask=False, train_semantic_cls=False, train_mask_out_mask=False,
 )
-
-
-class _ScaleGradFn(JGFunction):
-    """identity on the loss value; multiplies the gradient by the static fp16 loss scale (1 for bf16)."""
-
-    @staticmethod
-    def forward(ctx, x, s):
-        ctx.s = s
-        return x.clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        return g * ctx.s, None
 
 
 FORK_GAN_DEFAULT = True
@@ -119,10 +104,7 @@ class CUTModel(BaseModel):
                                       "segformer_attn_conv generators")
         if "segformer" in opt.G_netG:           # cut_model.py:205-210: enforced by the reference
             opt.alg_cut_nce_layers, opt.alg_cut_nce_T = "0,1,2,3", 0.2
-        bad = [d for d in opt.D_netDs if d not in ("basic", "projected_d")]
-        if bad or not opt.D_netDs:
-            raise NotImplementedError(f"D_netDs={opt.D_netDs!r}: 'basic' (PatchGAN) and 'projected_d' are built ('vision_aided' and the "
-                                      "depth / mask / sam / temporal discriminators need pretrained networks)")
+        check_discriminator_options(opt)
         if opt.alg_cut_netF != "mlp_sample":
             raise NotImplementedError(f"alg_cut_netF={opt.alg_cut_netF!r}")
         self.hdce = check_nce_options(opt)
@@ -167,21 +149,7 @@ class CUTModel(BaseModel):
         if opt.isTrain:
             self.netF = PatchSampleF(use_mlp=True, init_type=opt.model_init_type, init_gain=opt.model_init_gain, nc=opt.alg_cut_netF_nc)
             self.netF.set_device(self.device)
-            # gan_networks.define_D (:330-446): one network per entry of D_netDs, named D_B_<entry>
-            self.discriminators_names = []
-            for d in opt.D_netDs:
-                if d == "basic":
-                    net = NLayerDiscriminator(opt.model_output_nc, opt.D_ndf, n_layers=opt.D_n_layers)
-                else:
-                    from ..modules.projected_d import ProjectedDiscriminator
-
-                    # jg_projd_backbone: "lite0" (tf_efficientnet_lite0, the reference's feature network) | "standin" (tests);
-                    # jg_projd_pretrained: path of a timm tf_efficientnet_lite0 state_dict (the weights cannot be downloaded here)
-                    net = ProjectedDiscriminator(getattr(opt, "D_proj_network_type", "efficientnet"), interp=getattr(opt, "D_proj_interp", -1),
-                                                 img_size=opt.data_crop_size, backbone=getattr(opt, "jg_projd_backbone", "lite0"),
-                                                 pretrained_path=getattr(opt, "jg_projd_pretrained", ""))
-                setattr(self, "netD_B_" + d, net)
-                self.discriminators_names.append("D_B_" + d)
+            self.discriminators_names = define_discriminators(self, opt)
             self.model_names += ["F"] + self.discriminators_names
             # base_model.py:115-118; forward_GAN (base_gan_model.py:170-173) also pushes the real images through pools on every
             # iteration: they feed only the metrics, but they consume host random draws BEFORE the fake pool does
@@ -193,20 +161,7 @@ class CUTModel(BaseModel):
                       eps=opt.train_optim_eps)
             self.optimizer_G = self.make_optimizer(self.netG_A, **kw)
             kw["lr"] = opt.train_D_lr
-            # the reference chains every discriminator's parameters into ONE Adam (cut_model.py:378-395); one fused optimizer per
-            # discriminator arena with the same hyper-parameters is the same update
-            optD = []
-            for dn in self.discriminators_names:
-                o = self.make_optimizer(getattr(self, "net" + dn), **kw)
-                setattr(self, "optimizer_" + dn, o)
-                optD.append("optimizer_" + dn)
-                self.optimizers.append(o)
-                # base_gan_model.set_discriminators_info (:538-640): projected discriminators always train with the hinge objective
-                mode = "projected" if "projected" in dn else opt.train_gan_mode
-                calc = DiscriminatorGANLoss(getattr(self, "net" + dn), self.device, mode, opt.dataaug_D_label_smooth)
-                setattr(self, dn + "_loss_calculator", calc)
-                self.objects_to_update.append(calc)
-            self.optimizer_D = getattr(self, optD[0])
+            optD = define_D_optimizers(self, opt, kw)
             self.optimizers.append(self.optimizer_G)
             self.group_G = NetworkGroup(networks_to_optimize=["G_A", "F"], forward_functions=["forward"],
                                         backward_functions=["compute_G_loss"], loss_names_list=["loss_names_G"],

@@ -1,0 +1,66 @@
+"""What the models with discriminators share (cut_model, cm_gan_model): the networks of gan_networks.define_D, their loss calculators
+(base_gan_model.set_discriminators_info) and fused optimizers, the option checks and the loss-scale node of a GAN branch."""
+from __future__ import annotations
+
+from .._autograd import JGFunction
+from ..modules.discriminators import NLayerDiscriminator
+from ..modules.loss import DiscriminatorGANLoss
+
+
+class _ScaleGradFn(JGFunction):
+    """identity on the loss value; multiplies the gradient by the static fp16 loss scale (1 for bf16)."""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        ctx.s = s
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.s, None
+
+
+def check_discriminator_options(opt):
+    """the D_netDs entries this build accepts.  Host-only (no device)."""
+    bad = [d for d in opt.D_netDs if d not in ("basic", "projected_d")]
+    if bad or not opt.D_netDs:
+        raise NotImplementedError(f"D_netDs={opt.D_netDs!r}: 'basic' (PatchGAN) and 'projected_d' are built ('vision_aided' and the "
+                                  "depth / mask / sam / temporal discriminators need pretrained networks)")
+
+
+def define_discriminators(model, opt):
+    """gan_networks.define_D (:330-446): one network per entry of D_netDs, set as `model.netD_B_<entry>`; returns the names D_B_<entry>"""
+    names = []
+    for d in opt.D_netDs:
+        if d == "basic":
+            net = NLayerDiscriminator(opt.model_output_nc, opt.D_ndf, n_layers=opt.D_n_layers)
+        else:
+            from ..modules.projected_d import ProjectedDiscriminator
+
+            # jg_projd_backbone: "lite0" (tf_efficientnet_lite0, the reference's feature network) | "standin" (tests);
+            # jg_projd_pretrained: path of a timm tf_efficientnet_lite0 state_dict (the weights cannot be downloaded here)
+            net = ProjectedDiscriminator(getattr(opt, "D_proj_network_type", "efficientnet"), interp=getattr(opt, "D_proj_interp", -1),
+                                         img_size=opt.data_crop_size, backbone=getattr(opt, "jg_projd_backbone", "lite0"),
+                                         pretrained_path=getattr(opt, "jg_projd_pretrained", ""))
+        setattr(model, "netD_B_" + d, net)
+        names.append("D_B_" + d)
+    return names
+
+
+def define_D_optimizers(model, opt, kw):
+    """the reference chains every discriminator's parameters into ONE Adam (cut_model.py:378-395); one fused optimizer per discriminator
+    arena with the same hyper-parameters `kw` is the same update.  Sets `optimizer_<name>`, `<name>_loss_calculator` and
+    `model.optimizer_D` (the first), appends to `model.optimizers` / `model.objects_to_update`; returns the optimizers' attribute names."""
+    optD = []
+    for dn in model.discriminators_names:
+        o = model.make_optimizer(getattr(model, "net" + dn), **kw)
+        setattr(model, "optimizer_" + dn, o)
+        optD.append("optimizer_" + dn)
+        model.optimizers.append(o)
+        # base_gan_model.set_discriminators_info (:538-640): projected discriminators always train with the hinge objective
+        mode = "projected" if "projected" in dn else opt.train_gan_mode
+        calc = DiscriminatorGANLoss(getattr(model, "net" + dn), model.device, mode, opt.dataaug_D_label_smooth)
+        setattr(model, dn + "_loss_calculator", calc)
+        model.objects_to_update.append(calc)
+    model.optimizer_D = getattr(model, optD[0])
+    return optD

@@ -1698,6 +1698,80 @@ def cm_loss(F_next, F_cur, noisy_next, noisy_cur, cs_n, co_n, cs_c, co_c, mask, 
                            chub, float(lam), float(grad_scale))
 
 
+def _cm_gan_head_launch(Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, w, lam, grad_scale):
+    """(loss, dFn_cm, pred) of jg_cm_gan_head; every argument already contiguous / fp32 / int64 as the kernel reads it"""
+    B, Cc, H, W = noisy_n.shape
+    for name, t, dtype in (("F_cur", Fc, Fn.dtype), ("noisy_next", noisy_n, torch.float32), ("noisy_cur", noisy_c, torch.float32)):
+        if t.dtype != dtype or not t.is_contiguous():
+            raise TypeError(f"cm_gan_head: {name} must be contiguous {dtype}, got {t.dtype}")
+    if tuple(Fn.shape[:3]) != (B, H, W) or Fc.shape != Fn.shape or noisy_c.shape != noisy_n.shape or not Fn.is_contiguous():
+        raise ValueError(f"cm_gan_head: F {tuple(Fn.shape)} / {tuple(Fc.shape)} against noisy {tuple(noisy_n.shape)} / {tuple(noisy_c.shape)}")
+    for v in (cs_n, co_n, cs_c, co_c, w):
+        if v.numel() != B:
+            raise ValueError(f"cm_gan_head: per-sample vectors must hold {B} values, got {v.numel()}")
+    if mask is not None and mask.numel() != B * H * W:
+        raise ValueError(f"cm_gan_head: mask {tuple(mask.shape)} is not [B,1,H,W]")
+    loss = torch.zeros((), device=Fn.device, dtype=torch.float32)
+    dFn = torch.empty_like(Fn)
+    pred = torch.empty_like(Fn)
+    chub = 0.00054 * math.sqrt(Cc * H * W)
+    check(_lib.lib().jg_cm_gan_head(_dt(Fn), Fn.data_ptr(), Fc.data_ptr(), noisy_n.data_ptr(), noisy_c.data_ptr(), cs_n.data_ptr(),
+                                    co_n.data_ptr(), cs_c.data_ptr(), co_c.data_ptr(), _p(mask), w.data_ptr(), loss.data_ptr(),
+                                    dFn.data_ptr(), pred.data_ptr(), B, Cc, H, W, Fn.shape[-1], chub, lam, grad_scale, _st()), "jg_cm_gan_head")
+    return loss, dFn, pred
+
+
+def _cm_gan_head_bwd_launch(dFn, dpred, gloss, co_n, Cc):
+    """dF_next = gloss * dFn_cm + co_n[b] * dpred in one launch (jg_cm_gan_head_bwd); dpred None = no gradient reached pred, gloss None =
+    none reached the loss (a zero device scalar then)"""
+    B, H, W, cpad = dFn.shape
+    if dpred is not None:
+        dpred = dpred.contiguous()
+        if dpred.dtype != dFn.dtype or dpred.shape != dFn.shape:
+            raise TypeError(f"cm_gan_head: the gradient of pred must be {dFn.dtype} {tuple(dFn.shape)}, got {dpred.dtype} {tuple(dpred.shape)}")
+    g = torch.zeros((), device=dFn.device, dtype=torch.float32) if gloss is None else gloss.contiguous().float()
+    dF = torch.empty_like(dFn)
+    check(_lib.lib().jg_cm_gan_head_bwd(_dt(dFn), dFn.data_ptr(), _p(dpred), g.data_ptr(), co_n.data_ptr(), dF.data_ptr(), B, Cc, H, W, cpad,
+                                        _st()), "jg_cm_gan_head_bwd")
+    return dF
+
+
+class _CMGanHeadFn(JGFunction):
+    @staticmethod
+    def forward(ctx, Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, w, lam, grad_scale):
+        loss, dFn, pred = _cm_gan_head_launch(Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, w, lam, grad_scale)
+        ctx.save_for_backward(dFn, co_n)
+        ctx.Cc = noisy_n.shape[1]
+        ctx.set_materialize_grads(False)
+        return loss, pred
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss, gpred):
+        dFn, co_n = ctx.saved_tensors
+        if gloss is None and gpred is None:
+            return (None,) * 12
+        return (_cm_gan_head_bwd_launch(dFn, gpred, gloss, co_n, ctx.Cc),) + (None,) * 11
+
+
+def cm_gan_head(F_next, F_cur, noisy_next, noisy_cur, cs_n, co_n, cs_c, co_c, mask, loss_weights, lam=1.0, grad_scale=1.0):
+    """The seam of cm_gan (cm_gan_model.py: compute_cm_gan_loss): compute_cm_loss on the two UNet outputs exactly as `cm_loss` computes it
+    (`lam` scales this term only, its gradient carries `grad_scale`) AND the student's prediction pred = c_skip x_noisy + c_out F_next as
+    NHWC 16-bit, the discriminators' input, in ONE launch (jg_cm_gan_head).  Returns (loss, pred); both carry gradient, and the backward is
+    one launch too (jg_cm_gan_head_bwd): dF_next = g_loss * dFn_cm + c_out * dpred."""
+    _require_cuda(F_next, F_cur, noisy_next, noisy_cur, loss_weights)
+    m = None
+    if mask is not None:
+        m = mask.contiguous()
+        if m.dtype != torch.int64:
+            m = m.long()
+    f = lambda t: t.reshape(-1).contiguous().float()
+    args = (F_next, F_cur.detach(), noisy_next, noisy_cur, f(cs_n), f(co_n), f(cs_c), f(co_c), m, f(loss_weights), float(lam), float(grad_scale))
+    if TORCH_OPS_BOUNDARY:
+        return tuple(torch.ops.jg355.cm_gan_head(*args)[:2])
+    return _CMGanHeadFn.apply(*args)
+
+
 ECT_C = 1e-6                 # CMModel.c (cm_model.py:120)
 _ECT_MAX_BLOCKS = 64         # per-sample partial sums of jg_ect_loss (csrc/elementwise.hip)
 
@@ -2204,6 +2278,41 @@ def _ect_backward(ctx, gloss, gdFn):
 
 
 _op_ect_loss.register_autograd(_ect_backward, setup_context=_ect_setup)
+
+
+@torch.library.custom_op("jg355::cm_gan_head", mutates_args=())
+def _op_cm_gan_head(Fn: torch.Tensor, Fc: torch.Tensor, noisy_n: torch.Tensor, noisy_c: torch.Tensor, cs_n: torch.Tensor, co_n: torch.Tensor,
+                    cs_c: torch.Tensor, co_c: torch.Tensor, mask: Optional[torch.Tensor], w: torch.Tensor, lam: float,
+                    grad_scale: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(consistency loss, the student's prediction NHWC 16-bit, the loss's gradient w.r.t. Fn times grad_scale): jg_cm_gan_head"""
+    f = lambda t: t.reshape(-1).contiguous().float()
+    m = None if mask is None else mask.contiguous().long()
+    loss, dFn, pred = _cm_gan_head_launch(Fn.contiguous(), Fc.contiguous(), noisy_n.contiguous(), noisy_c.contiguous(), f(cs_n), f(co_n),
+                                          f(cs_c), f(co_c), m, f(w), lam, grad_scale)
+    return loss, pred, dFn
+
+
+@_op_cm_gan_head.register_fake
+def _(Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, w, lam, grad_scale):
+    e = lambda: torch.empty_like(Fn, memory_format=torch.contiguous_format)
+    return Fn.new_empty((), dtype=torch.float32), e(), e()
+
+
+def _cm_gan_head_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[2], inputs[5])
+    ctx.Cc = inputs[2].shape[1]
+    ctx.set_materialize_grads(False)
+
+
+def _cm_gan_head_backward(ctx, gloss, gpred, gdFn):
+    dFn, co_n = ctx.saved_tensors
+    g = None
+    if gloss is not None or gpred is not None:
+        g = _cm_gan_head_bwd_launch(dFn, gpred, gloss, co_n.reshape(-1).contiguous().float(), ctx.Cc)
+    return (g,) + (None,) * 11
+
+
+_op_cm_gan_head.register_autograd(_cm_gan_head_backward, setup_context=_cm_gan_head_setup)
 
 
 @torch.library.custom_op("jg355::ddpm_mse_loss", mutates_args=())

@@ -48,6 +48,16 @@ DEFAULTS = dict(
 )
 
 
+# model_type "cm_gan" only: the discriminator-side fields its training step reads (options/common_options.py, train_options.py);
+# alg_gan_lambda is forced to 0.01 by the model (cm_gan_model.py:22)
+CM_GAN_DEFAULTS = dict(
+    D_netDs=["projected_d", "basic"], D_ndf=64, D_n_layers=3, D_dropout=False, D_spectral=False, D_norm="instance", D_proj_interp=-1,
+    D_proj_network_type="efficientnet", train_gan_mode="lsgan", dataaug_D_label_smooth=False, dataaug_D_noise=0.0, dataaug_APA=False,
+    dataaug_D_diffusion=False, train_semantic_mask=False, train_semantic_cls=False, train_mask_out_mask=False,
+    train_temporal_criterion=False,
+)
+
+
 def _flatten(d, prefix, out):
     for k, v in d.items():
         key = f"{prefix}_{k}" if prefix else k
@@ -70,6 +80,9 @@ def opt_from_json(cfg, overrides=None, is_train=True):
     vals.update(flat)
     if overrides:
         vals.update(overrides)
+    if vals["model_type"] == "cm_gan":
+        for k, v in CM_GAN_DEFAULTS.items():
+            vals.setdefault(k, copy.deepcopy(v))
     opt = SimpleNamespace(**vals)
     opt.isTrain = is_train
     # options/common_options.py:1100-1108: "0,1" -> [0, 1]; "-1" -> []
