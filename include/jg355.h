@@ -638,6 +638,28 @@ int jg_pixel_loss(int dtype, const void* x, const void* y, float* ws, int64_t ws
                   int Cpad, int mode0, int mode1, float lambda0, float lambda1, jg_stream_t s);
 int jg_pixel_loss_bwd(int dtype, const void* x, const void* y, const float* g, void* dx, int S, int M, int C, int H, int W, int Cpad,
                       int mode0, int mode1, float lambda0, float lambda1, jg_stream_t s);
+/* Discriminator-input augmentations (dataaug_D_noise: util/util.py:296-300; adaptive pseudo augmentation: models/modules/loss.py:199-246).
+ *   jg_d_aug : for each of `nd` (1..JG_D_AUG_MAX) targets d, on 16-bit NHWC tensors [B, H, W, Cpad] with C valid channels,
+ *                out_d[b,h,w,c] = flag_d[b] ? alt_d[b,h,w,c] : src[b,h,w,c] + sigma * z[b,c,h,w]     (c < C; 0 in the padding channels)
+ *                flag_d[b]      = alt_d given && u_d[b] < *p_d                                        (written to flags_d: int32 [B])
+ *              src is read once for all targets and the noise z is shared by them.  The sum is taken in fp32 and rounded once; sigma == 0
+ *              passes src through bit for bit.  alt / p / flags / u / stream_ids are host arrays of nd entries (or NULL: no entry given);
+ *              p_d is an fp32 scalar in DEVICE memory.  z: fp32 [B, C, H, W] (the reference's layout and draw) or NULL: drawn in the kernel,
+ *              Philox4x32-10 on the two 32-bit words of the device tensor `key` with the counter (pixel, sample, noise_stream | channel
+ *              group << 16, call), Box-Muller in fp32.  u_d: fp32 [B] or NULL: word 0 of the counter (0, sample, stream_ids[d], call) mapped to
+ *              (0, 1).  The same (key, stream ids, call) give the same bits on every launch.
+ *              JG_ERR_BAD_ARG: C > Cpad, Cpad not a multiple of 8, src / out NULL or not 16-byte aligned, out aliasing src or alt, alt without
+ *              p or flags, a draw without key, stream ids above 65535 or shared between two drawn streams, nd outside 1..JG_D_AUG_MAX.
+ *   jg_apa_update : s = (n_pos - n_neg) / n over the n elements pred[i * stride] (counted as integers; stride 8 reads channel 0 of a
+ *              PatchGAN logit map, stride 1 every element of projected logits); adjust = sign(s - target);
+ *              p = p + (adjust * num) / den in fp32 in this order, then p < 0 -> p * 0, p > 1 -> 1.  p (read and written), adjust and
+ *              s are fp32 scalars in device memory.  One launch of one block. */
+#define JG_D_AUG_MAX 4
+int jg_d_aug(int dtype, const void* src, int nd, const void* const* alt, const float* const* p, void* const* out, int32_t* const* flags,
+             const float* const* u, const uint32_t* stream_ids, float sigma, const float* z, const uint32_t* key, uint32_t noise_stream,
+             uint32_t call, int B, int H, int W, int C, int Cpad, jg_stream_t s);
+int jg_apa_update(int dtype, const void* pred, int64_t n, int64_t stride, float* p, float* adjust, float* s_out, float target, float num,
+                  float den, jg_stream_t s);
 int jg_noise_level_embedding(const float* sigma, const float* W, float* emb, int Bn, int half, jg_stream_t s);
 /* gradient of the embedding with respect to W, ACCUMULATED into dW (the reference trains W: set_requires_grad(net, True),
  * base_model.py:1196-1217) */

@@ -4,7 +4,8 @@
 :341-419, `compute_G_loss_GAN(_generic)` :421-503) for the default configuration: G_netG='resnet', D_netDs=['basic'],
 alg_cut_netF='mlp_sample', alg_cut_nce_loss in {'monce', 'patchnce', 'SRC_hDCE'}, nce_idt, lsgan, optionally the paired pixel loss
 (alg_cut_supervised_loss 'L1' / 'MSE') and the identity pixel loss (alg_cut_MSE_idt), no semantic / multimodal / context / temporal /
-augmentation branches.
+augmentation branches; the discriminator regularisers dataaug_D_noise (Gaussian noise on both discriminator inputs) and dataaug_APA
+(adaptive pseudo augmentation) run through ops.d_aug / ops.apa_update.
 
 Per iteration (reference order): group G = {G_A, F}: fake = G(cat(real_A, real_B)); loss_G_tot = lambda_GAN * lsgan(D(fake_B), 1)
 + (NCE(real_A, fake_B) + NCE(real_B, idt_B)) / 2; backward; Adam step on G and on F (two fused launches).  Group D: fake from the
@@ -21,6 +22,7 @@ from ..modules.NCE.hdce import PatchHDCELoss
 from ..modules.NCE.patchnce import MoNCELoss, PatchNCELoss
 from ..modules.cut_networks import PatchSampleF
 from ..modules.resnet_generator import ResnetGenerator
+from ..options import D_AUG_DEFAULTS
 from ..util.image_pool import ImagePool
 from .base_model import BaseModel, NetworkGroup
 from .cut_step import CUTStepDriver, gate
@@ -32,7 +34,7 @@ CUT_DEFAULTS = dict(
     alg_cut_netF_nc=256, alg_cut_nce_T=0.07, alg_cut_HDCE_gamma=1.0, alg_cut_HDCE_gamma_min=1.0, alg_cut_num_patches=256, alg_cut_flip_equivariance=False, alg_cut_MSE_idt=False,
     alg_cut_supervised_loss=[""], alg_cut_lambda_supervised=1.0, alg_cut_lambda_MSE_idt=1.0, alg_gan_lambda=1.0, train_gan_mode="lsgan", D_netDs=["basic"], D_ndf=64, D_n_layers=3,
     D_dropout=False, D_spectral=False, dataaug_D_label_smooth=False, dataaug_D_noise=0.0, dataaug_APA=False,
-    dataaug_D_diffusion=False, train_semantic_mask=False, train_semantic_cls=False, train_mask_out_mask=False,
+    dataaug_D_diffusion=False, train_semantic_mask=False, train_semantic_cls=False, train_mask_out_mask=False, **D_AUG_DEFAULTS,
 )
 
 
@@ -75,6 +77,26 @@ def check_pixel_loss_options(opt):
     return mode_sup, mode_idt
 
 
+def check_d_aug_options(opt):
+    """dataaug_D_noise (cut_model.py:668-682) and dataaug_APA (base_gan_model.py:359-365, loss.py:199-246) as this build accepts them; returns
+    (sigma, apa).  Host-only (no device)."""
+    for k in ("dataaug_D_noise", "dataaug_APA", *D_AUG_DEFAULTS):
+        if not hasattr(opt, k):
+            setattr(opt, k, CUT_DEFAULTS[k])
+    sigma, apa = float(opt.dataaug_D_noise), bool(opt.dataaug_APA)
+    if sigma != sigma or sigma < 0.0:
+        raise ValueError(f"dataaug_D_noise={opt.dataaug_D_noise!r}: a standard deviation, >= 0")
+    if apa:
+        if getattr(opt, "isTrain", True) and int(getattr(opt, "train_pool_size", 50)) <= 0:      # the reference fails in ImagePool.get_random
+            raise ValueError("dataaug_APA draws its substitutes from the history pool: train_pool_size must be > 0")
+        if not 0.0 <= float(opt.dataaug_APA_p) <= 1.0 or int(opt.dataaug_APA_every) < 1 or not float(opt.dataaug_APA_nimg) > 0:
+            raise ValueError(f"dataaug_APA_p={opt.dataaug_APA_p!r} in [0, 1], dataaug_APA_every={opt.dataaug_APA_every!r} >= 1 and "
+                             f"dataaug_APA_nimg={opt.dataaug_APA_nimg!r} > 0 are required")
+        if len(opt.D_netDs) > ops.D_AUG_MAX:
+            raise NotImplementedError(f"dataaug_APA with more than {ops.D_AUG_MAX} discriminators")
+    return sigma, apa
+
+
 def cut_loss_names(opt, discriminators_names):
     """loss_names of the generator group in the reference's order (cut_model.py:444-455): G_tot, G_NCE, [G_supervised], [G_NCE_Y], [G_MSE_idt],
     G_GAN_*.  Host-only (no device)."""
@@ -110,11 +132,10 @@ class CUTModel(BaseModel):
         self.hdce = check_nce_options(opt)
         self.pixel_modes = check_pixel_loss_options(opt)      # (supervised term, identity term) of ops.pixel_loss
         for flag in ("model_multimodal", "alg_cut_flip_equivariance", "train_semantic_mask", "train_semantic_cls",
-                     "train_mask_out_mask", "dataaug_APA", "dataaug_D_diffusion"):
+                     "train_mask_out_mask", "dataaug_D_diffusion"):
             if getattr(opt, flag, False):
                 raise NotImplementedError(f"{flag} is outside the SURVEY.md 8 hot path")
-        if opt.dataaug_D_noise > 0:
-            raise NotImplementedError("noisy-D terms are outside the built path")
+        check_d_aug_options(opt)
         self.loss_G_SRC = 0.0      # cut_model.py:734-761: computed there, never part of loss_G_tot; not computed here
         # cut_model.py:752-766: with alg_cut_MSE_idt the identity contrastive term of SRC_hDCE runs with the hDCE weights too
         self.hdce_idt_weighted = bool(self.hdce and opt.alg_cut_MSE_idt)
@@ -178,6 +199,12 @@ class CUTModel(BaseModel):
         else:
             self.netG_A.jg_finalize(self.device, self.act_dtype)
         self.patch_ids_injection = None   # parity runs: callable(call_index, feat_shapes) -> list of id tensors
+        # parity runs: callable(kind, index) -> the draws of dataaug_D_noise / dataaug_APA as the reference makes them, or None (drawn in the
+        # kernel): ("z_fake", 0) / ("z_real", 0): fp32 [B, C, H, W] of torch.normal(0, 1);  ("u", d): fp32 [B] of discriminator d's torch.rand
+        self.d_aug_injection = None
+        self.d_noise, self.d_apa = check_d_aug_options(opt)
+        if self.d_apa and opt.isTrain:
+            self.visual_names.append(["APA_img"])
 
     # ---- inputs ---------------------------------------------------------------------------------------------------
     def set_input(self, data):
@@ -421,21 +448,73 @@ class CUTModel(BaseModel):
         self.driver.optimize_parameters()
 
     # ---- discriminator loss (base_gan_model.py:341-419) ------------------------------------------------------------------
+    def get_current_APA_prob(self):
+        """base_gan_model.py:329-339: APA_p / APA_adjust summed over the discriminators -- the one place that reads them on the host"""
+        out = {"APA_p": 0.0, "APA_adjust": 0.0}
+        for dn in self.discriminators_names:
+            calc = getattr(self, dn + "_loss_calculator")
+            out["APA_p"] += float(calc.adaptive_pseudo_augmentation_p)
+            out["APA_adjust"] += float(calc.adjust)
+        return out
+
+    def _d_aug_draw(self, kind, index=0):
+        return self.d_aug_injection(kind, index) if self.d_aug_injection is not None else None
+
+    def draw_D_fakes(self, reader_stream=None):
+        """The host-side half of compute_D_loss_generic (base_gan_model.py:341-365) for every discriminator, in the reference's draw order on
+        the pool's RNG: `fake_B_pool.query` (of fake_B_noisy with dataaug_D_noise: cut_model.py:668-682, the pool stores noisy images), then with
+        dataaug_APA `get_random` for the batch the flagged real samples come from.  Returns (fakes, alts or None), one entry per
+        discriminator.  With both options off: the pool queries and nothing else."""
+        src = self.fake_B
+        if self.d_noise > 0.0 or self.d_apa:
+            self._d_key = ops.d_aug_key(self.device) if self.d_aug_injection is None else None      # one Philox key per step
+        if self.d_noise > 0.0:          # call index 0: the fake batch is drawn first, as in the reference
+            (self.fake_B_noisy,), _ = ops.d_aug(self.fake_B, self.opt.model_output_nc, self.d_noise, z=self._d_aug_draw("z_fake"), key=self._d_key, call=0)
+            src = self.fake_B_noisy
+        fakes, alts = [], [] if self.d_apa else None
+        for _ in self.discriminators_names:
+            fakes.append(self.fake_B_pool.query(src, reader_stream=reader_stream).detach())
+            if self.d_apa:
+                alts.append(self.fake_B_pool.get_random(self.batch_size, reader_stream=reader_stream))
+                self.APA_img = alts[-1]
+        return fakes, alts
+
+    def real_D_operands(self, alts, outs=None):
+        """The real batch of every discriminator from ONE launch that reads real_B once: real_B + sigma z (call index 1, the same z for all of
+        them) where unflagged, the discriminator's own `alts` entry where its flag is set (flag = u < its p, both on the device).  `outs`: the
+        static operands of a captured graph, written in place.  Without APA all discriminators share one operand (`real_B_noisy`); with both
+        options off this is real_B itself and nothing is launched."""
+        n = len(self.discriminators_names)
+        if not (self.d_noise > 0.0 or self.d_apa):
+            return [self.real_B] * n
+        z = self._d_aug_draw("z_real") if self.d_noise > 0.0 else None
+        if not self.d_apa:
+            (self.real_B_noisy,), _ = ops.d_aug(self.real_B, self.opt.model_output_nc, self.d_noise, z=z, key=self._d_key, call=1, outs=outs)
+            return [self.real_B_noisy] * n
+        calcs = [getattr(self, dn + "_loss_calculator") for dn in self.discriminators_names]
+        us = [self._d_aug_draw("u", d) for d in range(n)]
+        reals, flags = ops.d_aug(self.real_B, self.opt.model_output_nc, self.d_noise, z=z, key=self._d_key, call=1, alts=alts,
+                                 ps=[c.apa_state[0:1] for c in calcs], us=None if us[0] is None else us, streams=[c.apa_stream for c in calcs], outs=outs)
+        for d, c in enumerate(calcs):
+            c.apa_flags = flags[d]
+        return reals
+
     def compute_D_loss(self):
         """base_gan_model.py:341-419: every discriminator draws ITS OWN fake batch from the history pool (compute_D_loss_generic)."""
         tot = 0
         drawn = self.driver.drawn_fakes          # early-D driver: drawn before the fork (same draw order)
+        fakes, alts = drawn if drawn is not None else self.draw_D_fakes()
+        reals = self.real_D_operands(alts)
         for i, dn in enumerate(self.discriminators_names):
-            fake = drawn[i] if drawn is not None else self.fake_B_pool.query(self.fake_B)
-            val = getattr(self, dn + "_loss_calculator").compute_loss_D(self._net(dn), self.real_B, fake, None)
+            val = getattr(self, dn + "_loss_calculator").compute_loss_D(self._net(dn), reals[i], fakes[i], None)
             setattr(self, "loss_D_GAN_" + dn, val)
             tot = tot + val
         self.loss_D_tot = _ScaleGradFn.apply(tot, self.loss_scale)
 
-    def _d_half_body(self, real, fakes, its):
-        """compute_D_loss + backward on given operands (the pool draws are the caller's)"""
+    def _d_half_body(self, reals, fakes, its):
+        """compute_D_loss + backward on given operands (the pool draws and the augmentations are the caller's)"""
         vals, tot = [], 0
-        for dn, fake in zip(self.discriminators_names, fakes):
+        for dn, real, fake in zip(self.discriminators_names, reals, fakes):
             val = getattr(self, dn + "_loss_calculator").compute_loss_D(self._net(dn), real, fake, None)
             vals.append(val)
             tot = tot + val

@@ -88,12 +88,16 @@ class GenGraphs:
 
 @dataclass
 class DiscGraph:
-    """discriminator half: one graph on a static real batch and one static pool draw per discriminator; `vals` / `tot`: its losses"""
+    """discriminator half: one graph on a static real batch and one static pool draw per discriminator; `vals` / `tot`: its losses.
+    `reals`: the real operand of every discriminator -- [real] * n, or with dataaug_APA one static tensor each (`real` is the first);
+    `preds`: every loss calculator's `pred_real` inside the graph (what `DiscriminatorGANLoss.update` reads after a replay)"""
     real: torch.Tensor
     fakes: list
     graph: object = None
     vals: list = None
     tot: torch.Tensor = None
+    reals: list = None
+    preds: list = None
 
 
 class CUTStepDriver:
@@ -134,7 +138,8 @@ class CUTStepDriver:
         return self.stream("wg_stream") if os.environ.get("JG_WGRAD_GROUP_STREAM", "0") == "1" else None
 
     def draw_pool_fakes(self, side):
-        """The history-pool draws of compute_D_loss, made on the MAIN stream before the side stream forks: `ImagePool.query` clones a stored
+        """The history-pool draws of compute_D_loss (`CUTModel.draw_D_fakes`: with dataaug_D_noise the noisy fake batch is formed first, by one
+        eager launch on the stream the draws run on; with dataaug_APA every query is followed by that discriminator's `get_random`), made on the MAIN stream before the side stream forks: `ImagePool.query` clones a stored
         image (a view of an earlier generator output, allocated on the main stream) and drops the last reference to it, so on the side
         stream the clone would only be queued when the caching allocator hands the block back to the main stream's pool (ADVICE r4:
         cross-stream use-after-free).  The drawn batches are then marked as in use by the side stream."""
@@ -145,11 +150,11 @@ class CUTStepDriver:
             m.fake_B.record_stream(side)
             side.wait_stream(torch.cuda.current_stream(m.device))
             with torch.cuda.stream(side):
-                return [m.fake_B_pool.query(m.fake_B, reader_stream=side).detach() for _ in m.discriminators_names]
-        fakes = [m.fake_B_pool.query(m.fake_B).detach() for _ in m.discriminators_names]
-        for f in fakes:
+                return m.draw_D_fakes(reader_stream=side)
+        fakes, alts = m.draw_D_fakes()
+        for f in fakes + (alts or []):
             f.record_stream(side)
-        return fakes
+        return fakes, alts
 
     def optimize_parameters(self):
         """the early-D step; `model.step_driver` says which form of each half ran"""
@@ -316,10 +321,16 @@ class CUTStepDriver:
         st = self.d_half.get(key, nets, lambda restore: self._d_capture(side, its, nets, restore))
         if st is None:
             return False
-        st.real.copy_(m.real_B)
-        for dst, f in zip(st.fakes, self.drawn_fakes):
+        fakes, alts = self.drawn_fakes
+        if m.d_noise > 0.0 or m.d_apa:      # one eager launch ahead of the replay writes the static real operand(s): no copy on top of it
+            m.real_D_operands(alts, outs=st.reals if m.d_apa else st.reals[:1])
+        else:
+            st.real.copy_(m.real_B)
+        for dst, f in zip(st.fakes, fakes):
             dst.copy_(f)
         st.graph.replay()
+        for dn, pred in zip(m.discriminators_names, st.preds):      # `update` (after the join) reads the prediction of THIS graph's replay
+            getattr(m, dn + "_loss_calculator").pred_real = pred
         for dn, val in zip(m.discriminators_names, st.vals):      # published as copies: the next replay overwrites the graph's own
             setattr(m, "loss_D_GAN_" + dn, val.detach().clone())
         m.loss_D_tot = st.tot.detach().clone()
@@ -328,9 +339,11 @@ class CUTStepDriver:
     def _d_capture(self, side, its, nets, restore):
         m = self.model
         st = DiscGraph(m.real_B.clone(), [m.fake_B.detach().clone() for _ in nets], torch.cuda.CUDAGraph())
+        st.reals = [st.real] + [m.real_B.clone() for _ in nets[1:]] if m.d_apa else [st.real] * len(nets)
         with torch.cuda.graph(st.graph, stream=side, capture_error_mode="thread_local"):      # other threads (pinned staging, checkpoint writer) may allocate
             ops.zero_pool_reset(m.device, True)
-            st.vals, st.tot = m._d_half_body(st.real, st.fakes, its)
+            st.vals, st.tot = m._d_half_body(st.reals, st.fakes, its)
+        st.preds = [getattr(m, dn + "_loss_calculator").pred_real for dn in m.discriminators_names]
         ops.zero_pool_reset(m.device)
         st.graph.replay()
         first = st.tot.detach().clone()

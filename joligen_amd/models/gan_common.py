@@ -59,7 +59,11 @@ def define_D_optimizers(model, opt, kw):
         model.optimizers.append(o)
         # base_gan_model.set_discriminators_info (:538-640): projected discriminators always train with the hinge objective
         mode = "projected" if "projected" in dn else opt.train_gan_mode
-        calc = DiscriminatorGANLoss(getattr(model, "net" + dn), model.device, mode, opt.dataaug_D_label_smooth)
+        calc = DiscriminatorGANLoss(getattr(model, "net" + dn), model.device, mode, opt.dataaug_D_label_smooth,
+                                    dataaug_APA=getattr(opt, "dataaug_APA", False), dataaug_APA_p=getattr(opt, "dataaug_APA_p", 0.0),
+                                    dataaug_APA_target=getattr(opt, "dataaug_APA_target", 0.6), train_batch_size=opt.train_batch_size,
+                                    dataaug_APA_nimg=getattr(opt, "dataaug_APA_nimg", 50), dataaug_APA_every=getattr(opt, "dataaug_APA_every", 4),
+                                    apa_stream=len(optD))      # Philox stream 1 + index: stream 0 is the noise's
         setattr(model, dn + "_loss_calculator", calc)
         model.objects_to_update.append(calc)
     model.optimizer_D = getattr(model, optD[0])

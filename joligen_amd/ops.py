@@ -1900,6 +1900,102 @@ def pixel_loss(x, y, C, modes, lambdas):
     return _PixelLossFn.apply(x, y.detach(), int(C), modes, lambdas)
 
 
+# ---- discriminator-input augmentations: dataaug_D_noise and adaptive pseudo augmentation (csrc/d_aug.hip) ----------------------------------
+D_AUG_MAX = 4                  # targets of one jg_d_aug launch (JG_D_AUG_MAX of include/jg355.h)
+D_AUG_NOISE_STREAM = 0         # Philox stream id of the noise; the flags of target d draw on stream 1 + d unless the caller says otherwise
+
+
+def d_aug_key(device):
+    """the 64-bit Philox key of jg_d_aug as a two-word device tensor, drawn on torch's generator for `device` (torch.manual_seed decides it;
+    the draw is legal inside a graph capture)"""
+    return torch.randint(-2 ** 31, 2 ** 31, (2,), device=device, dtype=torch.int32)
+
+
+def _d_aug_launch(src, C, sigma, z, key, noise_stream, call, alts, ps, us, streams, outs, flags):
+    """jg_d_aug on checked arguments: `outs` (and `flags`, with `alts`) are written in place; nothing is returned"""
+    import ctypes
+
+    _require_cuda(src, z, key, *outs, *(alts or ()), *(ps or ()), *(us or ()), *((flags,) if flags is not None else ()))
+    nd = len(outs)
+    B, H, W, cpad = src.shape
+    if not 1 <= nd <= D_AUG_MAX or (alts is not None and len(alts) != nd) or (alts is None and (ps is not None or us is not None)):
+        raise ValueError(f"d_aug: 1..{D_AUG_MAX} targets, one alt per target, p / u only with alt (got {nd} outputs)")
+    if alts is not None and (ps is None or len(ps) != nd or (us is not None and len(us) != nd) or flags is None or len(streams) != nd):
+        raise ValueError("d_aug: alt needs one p, one stream id (and, when injected, one u) per target, and a flags tensor")
+    for t in list(outs) + list(alts or ()):
+        if t.dtype != src.dtype or tuple(t.shape) != tuple(src.shape) or not t.is_contiguous():
+            raise TypeError(f"d_aug: every image must be contiguous {tuple(src.shape)} {src.dtype}, got {tuple(t.shape)} {t.dtype}")
+    if not src.is_contiguous() or not 1 <= int(C) <= cpad:
+        raise ValueError(f"d_aug: src must be a contiguous NHWC tensor with 1 <= C <= {cpad} (C = {C})")
+    if z is not None and (z.dtype != torch.float32 or tuple(z.shape) != (B, int(C), H, W) or not z.is_contiguous()):
+        raise TypeError(f"d_aug: z must be contiguous fp32 {(B, int(C), H, W)}, got {tuple(z.shape)} {z.dtype}")
+    if key is not None and (key.dtype != torch.int32 or key.numel() != 2):
+        raise TypeError("d_aug: key must hold two int32 words")
+    for t, what, n in [(t, "p", 1) for t in (ps or ())] + [(t, "u", B) for t in (us or ())]:
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise TypeError(f"d_aug: {what} must be contiguous fp32 with {n} element(s)")
+    if flags is not None and (flags.dtype != torch.int32 or tuple(flags.shape) != (nd, B) or not flags.is_contiguous()):
+        raise TypeError(f"d_aug: flags must be contiguous int32 {(nd, B)}")
+    arr = lambda ts: None if ts is None else (ctypes.c_void_p * nd)(*[t.data_ptr() for t in ts])
+    fl = None if flags is None else (ctypes.c_void_p * nd)(*[flags[d].data_ptr() for d in range(nd)])
+    sid = None if alts is None else (ctypes.c_uint32 * nd)(*[int(v) for v in streams])
+    check(_lib.lib().jg_d_aug(_dt(src), src.data_ptr(), nd, arr(alts), arr(ps), arr(outs), fl, arr(us), sid, float(sigma), _p(z), _p(key),
+                              int(noise_stream), int(call), B, H, W, int(C), cpad, _st()), "jg_d_aug")
+
+
+def d_aug(src, C, sigma=0.0, z=None, key=None, call=0, alts=None, ps=None, us=None, streams=None, outs=None, noise_stream=D_AUG_NOISE_STREAM):
+    """The discriminator inputs of a step from ONE launch (dataaug_D_noise: util/util.py:296-300; APA: models/modules/loss.py:199-212), on 16-bit
+    NHWC images [B, H, W, Cpad] with C valid channels: for every target d (one without `alts`, else one per entry)
+        out_d[b] = flag_d[b] ? alts[d][b] : src[b] + sigma * z[b],      flag_d[b] = u_d[b] < ps[d]  (ps[d]: fp32 scalar on the device)
+    z: fp32 [B, C, H, W] (injected) or None: drawn in the kernel from `key` (d_aug_key) at call index `call`, shared by all targets;
+    us: one fp32 [B] per target (injected) or None: drawn in the kernel on the Philox streams `streams` (default 1 + d).
+    outs: tensors to write (the static operands of a captured graph), default fresh ones.  Returns (outs, flags int32 [nd, B] or None).
+    Not differentiable: the reference detaches these inputs."""
+    nd = len(alts) if alts is not None else 1
+    src = src.detach()
+    if alts is not None:
+        alts = [a.detach() for a in alts]
+        streams = list(streams) if streams is not None else [1 + d for d in range(nd)]
+    if TORCH_OPS_BOUNDARY:
+        o, f = torch.ops.jg355.d_aug(src, list(alts or ()), list(ps or ()), list(us or ()), list(streams or ()), int(C), float(sigma), z, key,
+                                     int(noise_stream), int(call))
+        if outs is not None:
+            for dst, t in zip(outs, o):
+                dst.copy_(t)
+        return (list(outs) if outs is not None else list(o.unbind(0))), (f if alts is not None else None)
+    if outs is None:
+        outs = [torch.empty_like(src) for _ in range(nd)]
+    flags = torch.empty((nd, src.shape[0]), device=src.device, dtype=torch.int32) if alts is not None else None
+    _d_aug_launch(src, C, sigma, z, key, noise_stream, call, alts, ps, us, streams, list(outs), flags)
+    return list(outs), flags
+
+
+def _apa_update_launch(pred, state, n, stride, target, num, den):
+    _require_cuda(pred, state)
+    if state.dtype != torch.float32 or state.numel() != 3 or not state.is_contiguous():
+        raise TypeError("apa_update: state must be contiguous fp32 [3] = (p, adjust, s)")
+    if not pred.is_contiguous() or n < 1 or stride < 1 or (n - 1) * stride >= pred.numel():
+        raise ValueError(f"apa_update: {n} elements at stride {stride} do not fit the contiguous prediction {tuple(pred.shape)}")
+    sp = state.data_ptr()
+    check(_lib.lib().jg_apa_update(_dt(pred), pred.data_ptr(), int(n), int(stride), sp, sp + 4, sp + 8, float(target), float(num), float(den),
+                                   _st()), "jg_apa_update")
+
+
+def apa_update(pred, state, target, num, den, channel0=False):
+    """update_adaptive_pseudo_augmentation_p (models/modules/loss.py:214-231) in one launch, IN PLACE on `state` = fp32 [3] (p, adjust, s) on the
+    device: s = mean(sign(pred)), adjust = sign(s - target), p = clamp(p + adjust * num / den, 0, 1) with num = batch size * dataaug_APA_every,
+    den = dataaug_APA_nimg * 1000.  pred: the 16-bit prediction on the (substituted) real batch; channel0: an NHWC logit map whose channel 0 is
+    valid (PatchGAN), else every element (projected logits).  No host read."""
+    pred = pred.detach()
+    stride = pred.shape[-1] if channel0 else 1
+    n = pred.numel() // stride
+    if TORCH_OPS_BOUNDARY:
+        torch.ops.jg355.apa_update(pred, state, n, stride, float(target), float(num), float(den))
+    else:
+        _apa_update_launch(pred, state, n, stride, float(target), float(num), float(den))
+    return state
+
+
 class _ToNCHWFn(JGFunction):
     @staticmethod
     def forward(ctx, x, Cc):

@@ -17,6 +17,7 @@ tests/test_gpu_5_cutloss.py::test_cut_step_through_torch_ops holds the two forms
   gather_patches / scatter_patches, l2_normalize / _bwd, patch_nce / patch_nce_bwd      PatchSampleF + PatchNCE / MoNCE (Sinkhorn inside)
   patch_hdce / patch_hdce_bwd                SRC_hDCE: weights from the key Gram matrix + weighted contrastive loss, one fused kernel
   pixel_loss / pixel_loss_bwd                paired (supervised) and identity L1 / MSE between 16-bit images, both terms in one launch set
+  d_aug, apa_update                          dataaug_D_noise + adaptive pseudo augmentation: the discriminators' inputs of a step; the update of p
   gan_loss, hinge_loss                       GANLoss (lsgan / vanilla / wgangp) and the projected hinge; return (loss, d loss / d pred)
   spectral_weight / _bwd                     torch.nn.utils.spectral_norm: one power iteration, W / sigma; gradient through 1 / sigma
   bilinear2 / bilinear2_bwd                  F.interpolate(mode="bilinear", align_corners=...)
@@ -688,6 +689,38 @@ def _pl_backward(ctx, g):
 
 
 pixel_loss.register_autograd(_pl_backward, setup_context=_pl_setup)
+
+
+# ---- discriminator-input augmentations (not differentiable: the reference detaches their inputs) -----------------------------------------
+@op("jg355::d_aug", mutates_args=())
+def d_aug(src: T, alts: List[T], ps: List[T], us: List[T], streams: List[int], C: int, sigma: float, z: Optional[T], key: Optional[T],
+          noise_stream: int, call: int) -> Tuple[T, T]:
+    """ops.d_aug as a functional op: -> (out [nd, B, H, W, Cpad], flags int32 [nd, B]); nd = max(len(alts), 1); empty lists = not given"""
+    nd = max(len(alts), 1)
+    src = src.contiguous()
+    out = torch.empty((nd,) + tuple(src.shape), device=src.device, dtype=src.dtype)
+    flags = torch.zeros((nd, src.shape[0]), device=src.device, dtype=torch.int32)
+    has = len(alts) > 0
+    ops._d_aug_launch(src, C, sigma, z, key, noise_stream, call, [a.contiguous() for a in alts] if has else None, list(ps) if has else None,
+                      list(us) if has and len(us) else None, list(streams) if has else None, list(out.unbind(0)), flags if has else None)
+    return out, flags
+
+
+@d_aug.register_fake
+def _(src, alts, ps, us, streams, C, sigma, z, key, noise_stream, call):
+    nd = max(len(alts), 1)
+    return src.new_empty((nd,) + tuple(src.shape)), src.new_empty((nd, src.shape[0]), dtype=torch.int32)
+
+
+@op("jg355::apa_update", mutates_args=("state",))
+def apa_update(pred: T, state: T, n: int, stride: int, target: float, num: float, den: float) -> None:
+    """ops.apa_update: `state` = fp32 [3] (p, adjust, s) is updated in place from the n elements pred[i * stride]"""
+    ops._apa_update_launch(pred, state, n, stride, target, num, den)
+
+
+@apa_update.register_fake
+def _(pred, state, n, stride, target, num, den):
+    return None
 
 
 # ---- GAN objectives: (loss, d loss / d pred) -------------------------------------------------------------------------------------------------

@@ -58,6 +58,11 @@ CM_GAN_DEFAULTS = dict(
 )
 
 
+# model_type "cut": the settings of adaptive pseudo augmentation (options/train_options.py); dataaug_APA / dataaug_D_noise themselves default
+# in the model (cut_model.CUT_DEFAULTS)
+D_AUG_DEFAULTS = dict(dataaug_APA_target=0.6, dataaug_APA_p=0.0, dataaug_APA_every=4, dataaug_APA_nimg=50)
+
+
 def _flatten(d, prefix, out):
     for k, v in d.items():
         key = f"{prefix}_{k}" if prefix else k
@@ -83,6 +88,9 @@ def opt_from_json(cfg, overrides=None, is_train=True):
     if vals["model_type"] == "cm_gan":
         for k, v in CM_GAN_DEFAULTS.items():
             vals.setdefault(k, copy.deepcopy(v))
+    if vals["model_type"] == "cut":
+        for k, v in D_AUG_DEFAULTS.items():
+            vals.setdefault(k, v)
     opt = SimpleNamespace(**vals)
     opt.isTrain = is_train
     # options/common_options.py:1100-1108: "0,1" -> [0, 1]; "-1" -> []

@@ -61,5 +61,10 @@ class ImagePool:
     def __len__(self):
         return len(self.images)
 
-    def get_random(self, nb):
-        return torch.cat([self.images[self.rng.randint(0, len(self.images) - 1)].clone() for _ in range(nb)], 0)
+    def get_random(self, nb, reader_stream=None):
+        """`nb` stored images, one randint each (image_pool.py:64-72); reader_stream: as in `query`"""
+        picks = [self.images[self.rng.randint(0, len(self.images) - 1)] for _ in range(nb)]
+        if reader_stream is not None:
+            for image in picks:
+                image.record_stream(reader_stream)
+        return torch.cat(picks, 0)
