@@ -660,6 +660,40 @@ int jg_d_aug(int dtype, const void* src, int nd, const void* const* alt, const f
              uint32_t call, int B, int H, int W, int C, int Cpad, jg_stream_t s);
 int jg_apa_update(int dtype, const void* pred, int64_t n, int64_t stride, float* p, float* adjust, float* s_out, float target, float num,
                   float den, jg_stream_t s);
+/* dataaug_D_diffusion: Diffusion-GAN noise on the four backbone feature maps of the projected discriminator
+ * (models/modules/projected_d/diffusion.py, projector.py:531-556) and the adaptive update of its strength p (models/modules/loss.py:315-331).
+ * The state lives in DEVICE memory: p (fp32), Tn (int32 [2] = T, n), the tables a = sqrt(cumprod alpha) and b = sqrt(1 - cumprod alpha)
+ * (fp32 [JG_D_DIFFUSION_TABLE]), t_epl (int32 [JG_D_DIFFUSION_EPL]).  x / out / t_out / t_in / z / H / W / C are host arrays of `nl`
+ * (1..JG_D_DIFFUSION_MAX) entries; every map is 16-bit NHWC [B, H_l, W_l, C_l] with C_l % 8 == 0.
+ *   jg_d_diffusion        : out_l[b,h,w,c] = a[t_l[b,c]] * x_l[b,h,w,c] + (noise_std * b[t_l[b,c]]) * z_l[b,c,h,w], in fp32, rounded once; a
+ *                           channel with b[t] == 0 is a[t] * x alone (bit-exact pass-through at t = 0).  t_l[b,c] = t_epl[i] with i the top 6
+ *                           bits of a Philox4x32-10 word of the counter (c / 4, b, 8 + l, call), or t_in[l] (int32 [B, C_l], clamped to the
+ *                           tables); z_l Box-Muller normals of the counter (h * W + w, b, l | (c / 4) << 16, call), or z[l] (fp32
+ *                           [B, C_l, H_l, W_l]).  t_in / z may be NULL, or hold NULL entries: drawn from the two words of the device tensor
+ *                           `key`.  t_out[l] (int32 [B, C_l]) always receives the t used.  One launch for all levels.
+ *   jg_d_diffusion_bwd    : dx_l = a[t_l[b,c]] * dy_l, one launch for all levels.
+ *   jg_d_diffusion_update : one block.  p <- clip(p + (sign(*loss - 0.9) * num) / den, 0, 1), every step in fp32 in this order;
+ *                           T = clip(5 + rint(p * 495), 5, 500), n = min(rint(p * 64), 48) (products in fp32, ties to even);
+ *                           betas = fp32(linspace_fp64(1e-4, 1e-2, T)), alphas = 1 - betas in fp32, cumulative product in fp64 with a leading
+ *                           1, a[i] = fp32(sqrt(cp[i])), b[i] = fp32(sqrt(1 - cp[i])) for i <= T and 0 beyond;  t_epl[i < n] = k + 1 for the
+ *                           smallest integer k >= 1 with k (k + 1) >= u[i] T (T - 1) (the inverse CDF of prob_t = arange(T) / sum), t_epl[i >= n] =
+ *                           0.  u: fp32 [64] or NULL: word 0 of the counter (i, 0, 16, call) mapped to (0, 1).  *loss is an fp32 device scalar.
+ *   JG_ERR_BAD_ARG: nl outside 1..JG_D_DIFFUSION_MAX, C_l not a positive multiple of 8, a NULL or not 16-byte aligned map / t, out aliasing
+ *   x, t_out aliasing t_in, a draw without key, num < 0, den <= 0.  jg_d_diffusion_grid_cap: the most threads (16-byte groups in flight) a
+ *   launch uses; larger problems take further trips of the grid-stride loop. */
+#define JG_D_DIFFUSION_MAX 4
+#define JG_D_DIFFUSION_TABLE 501
+#define JG_D_DIFFUSION_EPL 64
+#define JG_D_DIFFUSION_T_MIN 5
+#define JG_D_DIFFUSION_T_MAX 500
+int jg_d_diffusion(int dtype, int nl, const void* const* x, void* const* out, int32_t* const* t_out, const int32_t* const* t_in,
+                   const float* const* z, const int* H, const int* W, const int* C, int B, const float* a, const float* b,
+                   const int32_t* t_epl, float noise_std, const uint32_t* key, uint32_t call, jg_stream_t s);
+int jg_d_diffusion_bwd(int dtype, int nl, const void* const* dy, void* const* dx, const int32_t* const* t, const int* H, const int* W,
+                       const int* C, int B, const float* a, jg_stream_t s);
+int jg_d_diffusion_update(float* p, int32_t* Tn, float* a, float* b, int32_t* t_epl, const float* loss, float num, float den, const float* u,
+                          const uint32_t* key, uint32_t call, jg_stream_t s);
+int jg_d_diffusion_grid_cap(void);
 int jg_noise_level_embedding(const float* sigma, const float* W, float* emb, int Bn, int half, jg_stream_t s);
 /* gradient of the embedding with respect to W, ACCUMULATED into dW (the reference trains W: set_requires_grad(net, True),
  * base_model.py:1196-1217) */

@@ -8,9 +8,8 @@
 //   counter = (pixel h * W + w,  sample b,  stream id | (group of 4 channels) << 16,  call index)
 // so that no two elements, samples, streams or call sites share a counter.  One call yields 4 words = 2 Box-Muller pairs = the normals
 // of 4 channels of one pixel; a flag's uniform is word 0 of the counter (0, b, stream id of that target, call index).
-//   uniform u = ((x >> 9) + 0.5) * 2^-23: 2^23 values, every one exact in fp32, inside the OPEN interval (0, 1): log(u) is finite
-//   normals   r = sqrt(-2 log(u0)), t = 2 pi u1: (r cos t, r sin t), all in fp32
-#include "common.h"
+// The generator, the uniform map and Box-Muller are in philox.h (shared with d_diffusion.hip).
+#include "philox.h"
 
 namespace {
 
@@ -25,28 +24,6 @@ struct DAugTargets {
   uint32_t stream[D_AUG_MAX];
   int n;
 };
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
-__device__ __forceinline__ float uniform_open(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }
-
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
-  const float r = sqrtf(-2.0f * logf(uniform_open(a)));
-  float sn, cs;
-  sincosf(6.283185307179586f * uniform_open(b), &sn, &cs);
-  n0 = r * cs;
-  n1 = r * sn;
-}
 
 // flags_d[b] = alt_d given && u_d[b] < p_d (0 for a target without alt); one thread per (target, sample)
 __global__ void d_aug_flags_kernel(DAugTargets t, const uint32_t* __restrict__ key, uint32_t call, int B) {
@@ -168,11 +145,6 @@ __global__ __launch_bounds__(1024) void apa_update_kernel(const T* __restrict__ 
     *adjust = adj;
     *s_out = s;
   }
-}
-
-inline int stream_grid(long total) {      // sized to the chip as the streaming passes of elementwise.hip are: 256 CUs x 16 blocks at most
-  const long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : b > 4096 ? 4096 : b);
 }
 
 }  // namespace

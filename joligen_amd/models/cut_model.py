@@ -5,7 +5,8 @@
 alg_cut_netF='mlp_sample', alg_cut_nce_loss in {'monce', 'patchnce', 'SRC_hDCE'}, nce_idt, lsgan, optionally the paired pixel loss
 (alg_cut_supervised_loss 'L1' / 'MSE') and the identity pixel loss (alg_cut_MSE_idt), no semantic / multimodal / context / temporal /
 augmentation branches; the discriminator regularisers dataaug_D_noise (Gaussian noise on both discriminator inputs) and dataaug_APA
-(adaptive pseudo augmentation) run through ops.d_aug / ops.apa_update.
+(adaptive pseudo augmentation) run through ops.d_aug / ops.apa_update, dataaug_D_diffusion (Diffusion-GAN noise on the projected
+discriminator's backbone features) inside that discriminator through ops.d_diffusion / ops.d_diffusion_update.
 
 Per iteration (reference order): group G = {G_A, F}: fake = G(cat(real_A, real_B)); loss_G_tot = lambda_GAN * lsgan(D(fake_B), 1)
 + (NCE(real_A, fake_B) + NCE(real_B, idt_B)) / 2; backward; Adam step on G and on F (two fused launches).  Group D: fake from the
@@ -26,7 +27,7 @@ from ..options import D_AUG_DEFAULTS
 from ..util.image_pool import ImagePool
 from .base_model import BaseModel, NetworkGroup
 from .cut_step import CUTStepDriver, gate
-from .gan_common import _ScaleGradFn, check_discriminator_options, define_D_optimizers, define_discriminators
+from .gan_common import _ScaleGradFn, check_d_diffusion_options, check_discriminator_options, define_D_optimizers, define_discriminators
 
 CUT_DEFAULTS = dict(
     alg_cut_lambda_NCE=1.0, alg_cut_lambda_SRC=0.0, alg_cut_nce_idt=True, alg_cut_nce_layers="0,4,8,12,16",
@@ -34,7 +35,8 @@ CUT_DEFAULTS = dict(
     alg_cut_netF_nc=256, alg_cut_nce_T=0.07, alg_cut_HDCE_gamma=1.0, alg_cut_HDCE_gamma_min=1.0, alg_cut_num_patches=256, alg_cut_flip_equivariance=False, alg_cut_MSE_idt=False,
     alg_cut_supervised_loss=[""], alg_cut_lambda_supervised=1.0, alg_cut_lambda_MSE_idt=1.0, alg_gan_lambda=1.0, train_gan_mode="lsgan", D_netDs=["basic"], D_ndf=64, D_n_layers=3,
     D_dropout=False, D_spectral=False, dataaug_D_label_smooth=False, dataaug_D_noise=0.0, dataaug_APA=False,
-    dataaug_D_diffusion=False, train_semantic_mask=False, train_semantic_cls=False, train_mask_out_mask=False, **D_AUG_DEFAULTS,
+    dataaug_D_diffusion=False, dataaug_D_diffusion_every=4, train_semantic_mask=False, train_semantic_cls=False, train_mask_out_mask=False,
+    **D_AUG_DEFAULTS,
 )
 
 
@@ -132,10 +134,13 @@ class CUTModel(BaseModel):
         self.hdce = check_nce_options(opt)
         self.pixel_modes = check_pixel_loss_options(opt)      # (supervised term, identity term) of ops.pixel_loss
         for flag in ("model_multimodal", "alg_cut_flip_equivariance", "train_semantic_mask", "train_semantic_cls",
-                     "train_mask_out_mask", "dataaug_D_diffusion"):
+                     "train_mask_out_mask"):
             if getattr(opt, flag, False):
                 raise NotImplementedError(f"{flag} is outside the SURVEY.md 8 hot path")
         check_d_aug_options(opt)
+        # dataaug_D_diffusion: the projected discriminator noises its own backbone features (modules/projected_d.Diffusion) and its loss
+        # calculator moves the strength; nothing of it lives in this model
+        self.d_diffusion = check_d_diffusion_options(opt)
         self.loss_G_SRC = 0.0      # cut_model.py:734-761: computed there, never part of loss_G_tot; not computed here
         # cut_model.py:752-766: with alg_cut_MSE_idt the identity contrastive term of SRC_hDCE runs with the hDCE weights too
         self.hdce_idt_weighted = bool(self.hdce and opt.alg_cut_MSE_idt)

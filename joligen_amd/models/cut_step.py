@@ -90,7 +90,8 @@ class GenGraphs:
 class DiscGraph:
     """discriminator half: one graph on a static real batch and one static pool draw per discriminator; `vals` / `tot`: its losses.
     `reals`: the real operand of every discriminator -- [real] * n, or with dataaug_APA one static tensor each (`real` is the first);
-    `preds`: every loss calculator's `pred_real` inside the graph (what `DiscriminatorGANLoss.update` reads after a replay)"""
+    `preds` / `lreals`: every loss calculator's `pred_real` / `loss_D_real` inside the graph (what `DiscriminatorGANLoss.update` reads after
+    a replay: APA the prediction, dataaug_D_diffusion the loss)"""
     real: torch.Tensor
     fakes: list
     graph: object = None
@@ -98,6 +99,7 @@ class DiscGraph:
     tot: torch.Tensor = None
     reals: list = None
     preds: list = None
+    lreals: list = None
 
 
 class CUTStepDriver:
@@ -329,8 +331,9 @@ class CUTStepDriver:
         for dst, f in zip(st.fakes, fakes):
             dst.copy_(f)
         st.graph.replay()
-        for dn, pred in zip(m.discriminators_names, st.preds):      # `update` (after the join) reads the prediction of THIS graph's replay
-            getattr(m, dn + "_loss_calculator").pred_real = pred
+        for dn, pred, lreal in zip(m.discriminators_names, st.preds, st.lreals):      # `update` (after the join) reads THIS graph's replay
+            calc = getattr(m, dn + "_loss_calculator")
+            calc.pred_real, calc.loss_D_real = pred, lreal
         for dn, val in zip(m.discriminators_names, st.vals):      # published as copies: the next replay overwrites the graph's own
             setattr(m, "loss_D_GAN_" + dn, val.detach().clone())
         m.loss_D_tot = st.tot.detach().clone()
@@ -344,7 +347,19 @@ class CUTStepDriver:
             ops.zero_pool_reset(m.device, True)
             st.vals, st.tot = m._d_half_body(st.reals, st.fakes, its)
         st.preds = [getattr(m, dn + "_loss_calculator").pred_real for dn in m.discriminators_names]
+        st.lreals = [getattr(m, dn + "_loss_calculator").loss_D_real for dn in m.discriminators_names]
         ops.zero_pool_reset(m.device)
+        # dataaug_D_diffusion draws a Philox key inside the graph: the canary's two replays start from the same generator state (as the
+        # generator half's do), which the caller gets back afterwards
+        rng = torch.cuda.get_rng_state(m.device) if getattr(m, "d_diffusion", False) else None
+        try:
+            return self._d_canary(side, st, restore, rng)
+        finally:
+            if rng is not None:
+                torch.cuda.set_rng_state(rng, m.device)
+
+    def _d_canary(self, side, st, restore, rng):
+        m = self.model
         st.graph.replay()
         first = st.tot.detach().clone()
         burst = torch.zeros(64, device=m.device)
@@ -355,6 +370,8 @@ class CUTStepDriver:
                 burst.add_(1.0)
         side.wait_stream(torch.cuda.default_stream(m.device))
         restore()                          # both replays start from the same power-iteration vectors / statistics
+        if rng is not None:
+            torch.cuda.set_rng_state(rng, m.device)
         st.graph.replay()
         self.d_half.check(first, st.tot.detach().clone(), 1e-3, "an untouched graph", ": export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 before the first HIP call")
         return st

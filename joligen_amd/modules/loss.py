@@ -2,7 +2,7 @@
 gan_mode='lsgan' (the train_gan_mode default: MSE against 1 / 0), 'vanilla' (BCE with logits), 'wgangp' (-/+ mean; the reference never
 adds its gradient penalty) and 'projected' (the hinge objective :77-84 that
 `set_discriminators_info` forces for projected discriminators, base_gan_model.py:544-545), and `DiscriminatorGANLoss` (:249-313)
-with adaptive pseudo augmentation (APA, `DiscriminatorLoss` :199-246) and without the D-diffusion augmentation.
+with adaptive pseudo augmentation (APA, `DiscriminatorLoss` :199-246) and the update of the D-diffusion augmentation (:315-331).
 lsgan predictions are NHWC logit maps whose channel 0 is valid (PatchGAN output padded to 8 channels); projected predictions are the
 concatenated logits [B, N] of the mini-discriminators (every element valid)."""
 from __future__ import annotations
@@ -42,10 +42,16 @@ class DiscriminatorGANLoss(nn.Module):
 
     def __init__(self, netD, device, train_gan_mode="lsgan", dataaug_D_label_smooth=False, dataaug_APA=False,
                  dataaug_D_diffusion=False, dataaug_APA_p=0.0, dataaug_APA_target=0.6, train_batch_size=1, dataaug_APA_nimg=50,
-                 dataaug_APA_every=4, apa_stream=1):
+                 dataaug_APA_every=4, apa_stream=1, dataaug_D_diffusion_every=4):
         super().__init__()
-        if dataaug_D_diffusion:
-            raise NotImplementedError("the D-diffusion augmentation is outside the built path")
+        self.dataaug_D_diffusion, self.dataaug_D_diffusion_every = bool(dataaug_D_diffusion), int(dataaug_D_diffusion_every or 0)
+        if self.dataaug_D_diffusion:
+            # loss.py:328-331 reaches into netD.freeze_feature_network.diffusion: only the convolutional projected discriminator built with
+            # diffusion_aug has one
+            if getattr(getattr(netD, "freeze_feature_network", None), "diffusion", None) is None:
+                raise NotImplementedError("the D-diffusion augmentation needs an EfficientNet projected discriminator built with diffusion_aug")
+            if self.dataaug_D_diffusion_every < 1:
+                raise ValueError(f"dataaug_D_diffusion_every={dataaug_D_diffusion_every!r}: >= 1 is required")
         self.netD, self.device = netD, device
         self.gan_mode = train_gan_mode
         self.criterionGAN = GANLoss(train_gan_mode, target_real_label=0.9 if dataaug_D_label_smooth else 1.0)
@@ -107,3 +113,6 @@ class DiscriminatorGANLoss(nn.Module):
         if self.dataaug_APA and niter % self.dataaug_APA_every < self.train_batch_size:
             ops.apa_update(self.pred_real, self.apa_state, self.dataaug_APA_target, self.train_batch_size * self.dataaug_APA_every,
                            self.dataaug_APA_nimg * 1000, channel0=self.gan_mode != "projected")
+        if self.dataaug_D_diffusion and niter % self.dataaug_D_diffusion_every < self.train_batch_size:
+            # loss.py:315-331: p moves with sign(loss_D_real - 0.9), then update_T; one launch on the device scalar, no host read
+            self.netD.freeze_feature_network.diffusion.update(self.loss_D_real, self.train_batch_size * self.dataaug_D_diffusion_every)

@@ -700,11 +700,50 @@ class FeatureFusionBlockMatrix(nn.Module):
         return self.out_conv(out)
 
 
+class Diffusion(nn.Module):
+    """projected_d/diffusion.py:84-159 (`Diffusion`, linear schedule, Gaussian noise) with its state on the device: the strength p, T, n, the
+    tables alphas_bar_sqrt / one_minus_alphas_bar_sqrt and t_epl are buffers that `update` rewrites IN PLACE by one launch
+    (ops.d_diffusion_update) and the forward's kernel reads -- so a captured hipGraph that holds the forward sees every update, and no step
+    waits for the host.  The buffers are not persistent: as in the reference (plain attributes), p is not part of a checkpoint.
+    `forward` noises the four feature maps in ONE launch (the reference: one call per map); t and the noise are drawn in the kernel from a
+    key drawn on torch's generator (legal inside a capture), or injected for parity runs:
+      inject_t : per map an int32 [B, C] (np.random.choice(t_epl) of the reference), inject_z : per map an fp32 [B, C, H, W] (its
+      torch.randn_like), inject_u : fp32 [64], the uniforms of the next update's inverse-CDF draw of t_epl"""
+
+    def __init__(self, t_min=5, t_max=500, noise_std=0.5):
+        super().__init__()
+        if (t_min, t_max) != (5, 500):
+            raise NotImplementedError("the update kernel is built for t_min = 5, t_max = 500 (projector.py:533-535)")
+        self.t_min, self.t_max, self.noise_std = t_min, t_max, float(noise_std)
+        st = ops.DDiffusionState.fresh("cpu")
+        for name, t in zip(("p", "Tn", "alphas_bar_sqrt", "one_minus_alphas_bar_sqrt", "t_epl"), st.tensors()):
+            self.register_buffer(name, t, persistent=False)
+        self.inject_t = self.inject_z = self.inject_u = None
+        self.t_used = None             # the int32 [B, C] tensors of the last forward
+
+    @property
+    def state(self):
+        return ops.DDiffusionState(self.p, self.Tn, self.alphas_bar_sqrt, self.one_minus_alphas_bar_sqrt, self.t_epl)
+
+    def forward(self, feats):
+        drawn = self.inject_t is None or self.inject_z is None
+        outs, self.t_used = ops.d_diffusion(feats, self.state, self.noise_std, key=ops.d_aug_key(feats[0].device) if drawn else None,
+                                            ts=self.inject_t, zs=self.inject_z)
+        return outs
+
+    def update(self, loss_real, batch_times_every):
+        """loss.py:321-331: p moves with sign(loss_D_real - 0.9); update_T follows, all on the device"""
+        ops.d_diffusion_update(self.state, loss_real, batch_times_every, u=self.inject_u)
+
+
 class Proj(nn.Module):
     """projector.py:490-589 with proj_type 2: frozen backbone -> CCM (1x1 convs to cout * (1, 2, 4, 8)) -> CSM (top-down fusion)."""
 
-    def __init__(self, cout=64, expand=True, interp=256, backbone="lite0"):
+    def __init__(self, cout=64, expand=True, interp=256, backbone="lite0", diffusion_aug=False):
         super().__init__()
+        self.diffusion_aug = bool(diffusion_aug)
+        if self.diffusion_aug:             # projector.py:531-536
+            self.diffusion = Diffusion(t_min=5, t_max=500, noise_std=0.5)
         w = TF_EFFICIENTNET_LITE0_WIDTHS
         if backbone == "lite0":        # the reference's architecture (timm tf_efficientnet_lite0), weights to be loaded
             pre = make_efficientnet_lite0()
@@ -735,6 +774,8 @@ class Proj(nn.Module):
         o1 = p.layer1(o0)
         o2 = p.layer2(o1)
         o3 = p.layer3(o2)
+        if self.diffusion_aug:             # projector.py:551-556: only the copies handed to the channel mixing are noised
+            o0, o1, o2, o3 = self.diffusion([o0, o1, o2, o3])
         c0, c1, c2, c3 = s.layer0_ccm(o0), s.layer1_ccm(o1), s.layer2_ccm(o2), s.layer3_ccm(o3)
         m3 = s.layer3_csm(c3)
         m2 = s.layer2_csm(m3, c2)
@@ -746,8 +787,12 @@ class Proj(nn.Module):
 class ProjectedDiscriminator(nn.Module):
     """discriminator.py:233-286.  forward(x: [B, S, S, 8] 16-bit NHWC image, 3 valid channels) -> logits [B, N]."""
 
-    def __init__(self, projector_model="efficientnet", interp=-1, img_size=256, cout=64, expand=True, backbone="lite0", pretrained_path=""):
+    def __init__(self, projector_model="efficientnet", interp=-1, img_size=256, cout=64, expand=True, backbone="lite0", pretrained_path="",
+                 diffusion_aug=False):
         super().__init__()
+        if diffusion_aug and projector_model != "efficientnet":      # options/train_options.py:776
+            raise ValueError("dataaug_D_diffusion is not compatible with the ViT projectors (D_proj_network_type)")
+        self.diffusion_aug = bool(diffusion_aug)
         if projector_model not in ("efficientnet", "vitsmall"):
             raise NotImplementedError(f"D_proj_network_type={projector_model!r}: the convolutional ('efficientnet' = tf_efficientnet_lite0) and the ViT "
                                       "('vitsmall' = vit_small_patch16_224) projectors are built; vitbase / CLIP / SigLIP / DINOv2 / SegFormer / depth "
@@ -775,7 +820,7 @@ class ProjectedDiscriminator(nn.Module):
             self.per_sample = True          # LayerNorm backbone, Conv1d / MLP projector and heads: no batch statistics, no spectral norm (loss.py)
             return
         self.backbone = backbone
-        self.freeze_feature_network = Proj(cout=cout, expand=expand, interp=size, backbone=backbone)
+        self.freeze_feature_network = Proj(cout=cout, expand=expand, interp=size, backbone=backbone, diffusion_aug=diffusion_aug)
         self.freeze_feature_network.requires_grad_(False)
         if pretrained_path:
             self.load_pretrained_backbone(pretrained_path)

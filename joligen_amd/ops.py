@@ -1996,6 +1996,169 @@ def apa_update(pred, state, target, num, den, channel0=False):
     return state
 
 
+# ---- dataaug_D_diffusion: Diffusion-GAN noise on the projected discriminator's backbone features (csrc/d_diffusion.hip) ---------------------
+D_DIFFUSION_MAX, D_DIFFUSION_TABLE, D_DIFFUSION_EPL = 4, 501, 64      # JG_D_DIFFUSION_* of include/jg355.h
+
+
+class DDiffusionState:
+    """the device state of the augmentation: p fp32 [1] (strength), Tn int32 [2] (T, n), the tables a = sqrt(cumprod alpha) and
+    b = sqrt(1 - cumprod alpha) fp32 [501], t_epl int32 [64].  `fresh` is the reference's start p = 0: T = 5, t_epl = 0, a[0] = 1, b[0] = 0"""
+
+    __slots__ = ("p", "Tn", "a", "b", "t_epl")
+
+    def __init__(self, p, Tn, a, b, t_epl):
+        self.p, self.Tn, self.a, self.b, self.t_epl = p, Tn, a, b, t_epl
+
+    @classmethod
+    def fresh(cls, device):
+        st = cls(torch.zeros(1, device=device), torch.tensor([5, 0], device=device, dtype=torch.int32),
+                 torch.zeros(D_DIFFUSION_TABLE, device=device), torch.zeros(D_DIFFUSION_TABLE, device=device),
+                 torch.zeros(D_DIFFUSION_EPL, device=device, dtype=torch.int32))
+        st.a[0] = 1.0
+        return st
+
+    def tensors(self):
+        return self.p, self.Tn, self.a, self.b, self.t_epl
+
+    def check(self):
+        for t, dt, n, what in ((self.p, torch.float32, 1, "p"), (self.Tn, torch.int32, 2, "Tn"), (self.a, torch.float32, D_DIFFUSION_TABLE, "a"),
+                               (self.b, torch.float32, D_DIFFUSION_TABLE, "b"), (self.t_epl, torch.int32, D_DIFFUSION_EPL, "t_epl")):
+            if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+                raise TypeError(f"d_diffusion: state.{what} must be contiguous {dt} with {n} element(s), got {tuple(t.shape)} {t.dtype}")
+        _require_cuda(*self.tensors())
+
+
+def d_diffusion_grid_cap():
+    """the most 16-byte groups (8 elements each) one jg_d_diffusion launch has in flight; larger problems loop"""
+    return int(_lib.lib().jg_d_diffusion_grid_cap())
+
+
+def _dd_arrays(maps):
+    import ctypes
+
+    n = len(maps)
+    I = ctypes.c_int * n
+    return I(*[m.shape[1] for m in maps]), I(*[m.shape[2] for m in maps]), I(*[m.shape[3] for m in maps])
+
+
+def _dd_ptrs(ts, n):
+    import ctypes
+
+    return None if ts is None else (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _dd_check_maps(xs, what):
+    n = len(xs)
+    if not 1 <= n <= D_DIFFUSION_MAX:
+        raise ValueError(f"{what}: 1..{D_DIFFUSION_MAX} feature maps, got {n}")
+    _require_cuda(*xs)
+    for x in xs:
+        if x.dim() != 4 or x.dtype != xs[0].dtype or x.shape[0] != xs[0].shape[0] or not x.is_contiguous() or x.numel() == 0:
+            raise TypeError(f"{what}: every map must be a contiguous NHWC tensor of one 16-bit dtype and one batch size, got {tuple(x.shape)} {x.dtype}")
+    return n, xs[0].shape[0]
+
+
+def _d_diffusion_launch(xs, a, b, t_epl, noise_std, key, call, ts, zs, outs, t_outs):
+    """jg_d_diffusion on checked tensors: `outs` and `t_outs` are written in place"""
+    n, B = _dd_check_maps(xs, "d_diffusion")
+    for grp, what in ((ts, "ts"), (zs, "zs")):
+        if grp is not None and len(grp) != n:
+            raise ValueError(f"d_diffusion: {what} needs one entry per map (None: drawn)")
+    for l, x in enumerate(xs):
+        C = x.shape[3]
+        t = None if ts is None else ts[l]
+        z = None if zs is None else zs[l]
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (B, C) or not t.is_contiguous()):
+            raise TypeError(f"d_diffusion: t of level {l} must be contiguous int32 {(B, C)}, got {tuple(t.shape)} {t.dtype}")
+        if z is not None and (z.dtype != torch.float32 or tuple(z.shape) != (B, C, x.shape[1], x.shape[2]) or not z.is_contiguous()):
+            raise TypeError(f"d_diffusion: z of level {l} must be contiguous fp32 {(B, C, x.shape[1], x.shape[2])}, got {tuple(z.shape)} {z.dtype}")
+        _require_cuda(t, z)
+    if key is not None and (key.dtype != torch.int32 or key.numel() != 2):
+        raise TypeError("d_diffusion: key must hold two int32 words")
+    _require_cuda(key)
+    H, W, C = _dd_arrays(xs)
+    check(_lib.lib().jg_d_diffusion(_dt(xs[0]), n, _dd_ptrs(xs, n), _dd_ptrs(outs, n), _dd_ptrs(t_outs, n), _dd_ptrs(ts, n), _dd_ptrs(zs, n), H, W, C, B,
+                                    a.data_ptr(), b.data_ptr(), t_epl.data_ptr(), float(noise_std), _p(key), int(call), _st()), "jg_d_diffusion")
+
+
+def _d_diffusion_bwd_launch(dys, t_saved, a):
+    n, B = _dd_check_maps(dys, "d_diffusion_bwd")
+    dxs = [torch.empty_like(d) for d in dys]
+    H, W, C = _dd_arrays(dys)
+    check(_lib.lib().jg_d_diffusion_bwd(_dt(dys[0]), n, _dd_ptrs(dys, n), _dd_ptrs(dxs, n), _dd_ptrs(t_saved, n), H, W, C, B, a.data_ptr(), _st()),
+          "jg_d_diffusion_bwd")
+    return dxs
+
+
+class _DDiffusionFn(JGFunction):
+    """the noised copies of up to four feature maps from one launch; saves only the t it used.  The backward reads the table `a` as it is
+    THEN: an update between a forward and its backward would change it, and the step drivers update after both (as the reference does)"""
+
+    @staticmethod
+    def forward(ctx, state, noise_std, key, call, ts, zs, *xs):
+        xs = [x.contiguous() for x in xs]
+        outs = [torch.empty_like(x) for x in xs]
+        t_outs = [torch.empty((x.shape[0], x.shape[3]), device=x.device, dtype=torch.int32) for x in xs]
+        _d_diffusion_launch(xs, state.a, state.b, state.t_epl, noise_std, key, call, ts, zs, outs, t_outs)
+        ctx.a = state.a
+        ctx.save_for_backward(*t_outs)
+        ctx.mark_non_differentiable(*t_outs)
+        return (*outs, *t_outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *g):
+        n = len(ctx.saved_tensors)
+        dxs = _d_diffusion_bwd_launch([d.contiguous() for d in g[:n]], list(ctx.saved_tensors), ctx.a)
+        return (None,) * 6 + tuple(dxs)
+
+
+def d_diffusion(xs, state, noise_std, key=None, ts=None, zs=None, call=0):
+    """Diffusion.forward of the reference (projected_d/diffusion.py:139-159) on up to four 16-bit NHWC feature maps [B, H_l, W_l, C_l]
+    (C_l % 8 == 0) in ONE launch: out_l = a[t_l] * x_l + (noise_std * b[t_l]) * z_l with one t per (sample, channel), taken from `state`
+    (DDiffusionState) on the device.  ts: per level an int32 [B, C_l] (injected) or None: t = t_epl[6 random bits], drawn in the kernel from
+    `key` (d_aug_key); zs: per level an fp32 [B, C_l, H_l, W_l] (injected) or None: drawn in the kernel.  Returns (outs, ts_used).
+    Differentiable in xs (dx_l = a[t_l] * dy_l, one launch for all levels)."""
+    xs = list(xs)
+    state.check()
+    n = len(xs)
+    if TORCH_OPS_BOUNDARY:
+        if (ts is not None and any(t is None for t in ts)) or (zs is not None and any(z is None for z in zs)):
+            raise ValueError("d_diffusion through torch.ops: ts / zs are given for every level or not at all")
+        res = torch.ops.jg355.d_diffusion(xs, state.a, state.b, state.t_epl, float(noise_std), key, list(ts or ()), list(zs or ()), int(call))
+        return list(res[:n]), list(res[n:])
+    res = _DDiffusionFn.apply(state, float(noise_std), key, int(call), None if ts is None else list(ts), None if zs is None else list(zs), *xs)
+    return list(res[:n]), list(res[n:])
+
+
+def _d_diffusion_update_launch(p, Tn, a, b, t_epl, loss, num, den, u, key, call):
+    _require_cuda(loss, u, key)
+    if loss.dtype != torch.float32 or loss.numel() != 1:
+        raise TypeError(f"d_diffusion_update: loss_real must be an fp32 scalar on the device, got {tuple(loss.shape)} {loss.dtype}")
+    if u is not None and (u.dtype != torch.float32 or u.numel() != D_DIFFUSION_EPL or not u.is_contiguous()):
+        raise TypeError(f"d_diffusion_update: u must be contiguous fp32 [{D_DIFFUSION_EPL}]")
+    if key is not None and (key.dtype != torch.int32 or key.numel() != 2):
+        raise TypeError("d_diffusion_update: key must hold two int32 words")
+    check(_lib.lib().jg_d_diffusion_update(p.data_ptr(), Tn.data_ptr(), a.data_ptr(), b.data_ptr(), t_epl.data_ptr(), loss.data_ptr(), float(num),
+                                           float(den), _p(u), _p(key), int(call), _st()), "jg_d_diffusion_update")
+
+
+def d_diffusion_update(state, loss_real, batch_times_every, u=None, key=None, call=0):
+    """DiscriminatorGANLoss.update's diffusion branch + Diffusion.update_T (loss.py:315-331, diffusion.py:125-137) in one launch, IN PLACE on
+    `state`: p <- clip(p + sign(loss_real - 0.9) * batch_times_every / (100 * 1000), 0, 1) in fp32, then T, n, the tables and t_epl from p.
+    loss_real: fp32 scalar on the device (no host read); u: fp32 [64] uniforms of t_epl's inverse-CDF draw (injected) or None: drawn in the
+    kernel from `key` (default: a fresh d_aug_key)."""
+    state.check()
+    loss = loss_real.detach().reshape(1)
+    if u is None and key is None:
+        key = d_aug_key(loss.device)
+    if TORCH_OPS_BOUNDARY:
+        torch.ops.jg355.d_diffusion_update(*state.tensors(), loss, float(batch_times_every), 100.0 * 1000.0, u, key, int(call))
+    else:
+        _d_diffusion_update_launch(*state.tensors(), loss, float(batch_times_every), 100.0 * 1000.0, u, key, int(call))
+    return state
+
+
 class _ToNCHWFn(JGFunction):
     @staticmethod
     def forward(ctx, x, Cc):

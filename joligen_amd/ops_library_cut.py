@@ -18,6 +18,7 @@ tests/test_gpu_5_cutloss.py::test_cut_step_through_torch_ops holds the two forms
   patch_hdce / patch_hdce_bwd                SRC_hDCE: weights from the key Gram matrix + weighted contrastive loss, one fused kernel
   pixel_loss / pixel_loss_bwd                paired (supervised) and identity L1 / MSE between 16-bit images, both terms in one launch set
   d_aug, apa_update                          dataaug_D_noise + adaptive pseudo augmentation: the discriminators' inputs of a step; the update of p
+  d_diffusion / _bwd, d_diffusion_update     dataaug_D_diffusion: the noised backbone features of the projected discriminator; the update of its state
   gan_loss, hinge_loss                       GANLoss (lsgan / vanilla / wgangp) and the projected hinge; return (loss, d loss / d pred)
   spectral_weight / _bwd                     torch.nn.utils.spectral_norm: one power iteration, W / sigma; gradient through 1 / sigma
   bilinear2 / bilinear2_bwd                  F.interpolate(mode="bilinear", align_corners=...)
@@ -720,6 +721,60 @@ def apa_update(pred: T, state: T, n: int, stride: int, target: float, num: float
 
 @apa_update.register_fake
 def _(pred, state, n, stride, target, num, den):
+    return None
+
+
+# ---- dataaug_D_diffusion: noise on the backbone features of the projected discriminator ----------------------------------------------------
+@op("jg355::d_diffusion", mutates_args=())
+def d_diffusion(xs: List[T], a: T, b: T, t_epl: T, noise_std: float, key: Optional[T], ts: List[T], zs: List[T], call: int) -> List[T]:
+    """ops.d_diffusion as a functional op: -> the n noised maps followed by the n int32 [B, C_l] tensors of the t used; ts / zs: one entry
+    per map (injected) or empty (drawn in the kernel from `key`)"""
+    xs = [x.contiguous() for x in xs]
+    outs = [torch.empty_like(x) for x in xs]
+    t_outs = [torch.empty((x.shape[0], x.shape[3]), device=x.device, dtype=torch.int32) for x in xs]
+    ops._d_diffusion_launch(xs, a, b, t_epl, noise_std, key, call, list(ts) if len(ts) else None, list(zs) if len(zs) else None, outs, t_outs)
+    return outs + t_outs
+
+
+@d_diffusion.register_fake
+def _(xs, a, b, t_epl, noise_std, key, ts, zs, call):
+    return [torch.empty_like(x, memory_format=torch.contiguous_format) for x in xs] + [x.new_empty((x.shape[0], x.shape[3]), dtype=torch.int32) for x in xs]
+
+
+@op("jg355::d_diffusion_bwd", mutates_args=())
+def d_diffusion_bwd(dys: List[T], ts: List[T], a: T) -> List[T]:
+    """dx_l = a[t_l[b, c]] * dy_l for every level in one launch"""
+    return ops._d_diffusion_bwd_launch([d.contiguous() for d in dys], list(ts), a)
+
+
+@d_diffusion_bwd.register_fake
+def _(dys, ts, a):
+    return [torch.empty_like(d, memory_format=torch.contiguous_format) for d in dys]
+
+
+def _dd_setup(ctx, inputs, output):
+    n = len(inputs[0])
+    ctx.save_for_backward(inputs[1], *output[n:])
+    ctx.n_inj = (len(inputs[6]), len(inputs[7]))      # the gradient of a list input is a list of its length
+
+
+def _dd_backward(ctx, grads):
+    a, *ts = ctx.saved_tensors
+    n = len(ts)
+    return torch.ops.jg355.d_diffusion_bwd(list(grads[:n]), ts, a), None, None, None, None, None, [None] * ctx.n_inj[0], [None] * ctx.n_inj[1], None
+
+
+d_diffusion.register_autograd(_dd_backward, setup_context=_dd_setup)
+
+
+@op("jg355::d_diffusion_update", mutates_args=("p", "Tn", "a", "b", "t_epl"))
+def d_diffusion_update(p: T, Tn: T, a: T, b: T, t_epl: T, loss: T, num: float, den: float, u: Optional[T], key: Optional[T], call: int) -> None:
+    """ops.d_diffusion_update: the device state (p, Tn = (T, n), the tables a / b, t_epl) is rewritten in place from the fp32 scalar `loss`"""
+    ops._d_diffusion_update_launch(p, Tn, a, b, t_epl, loss, num, den, u, key, call)
+
+
+@d_diffusion_update.register_fake
+def _(p, Tn, a, b, t_epl, loss, num, den, u, key, call):
     return None
 
 

@@ -61,6 +61,8 @@ CM_GAN_DEFAULTS = dict(
 # model_type "cut": the settings of adaptive pseudo augmentation (options/train_options.py); dataaug_APA / dataaug_D_noise themselves default
 # in the model (cut_model.CUT_DEFAULTS)
 D_AUG_DEFAULTS = dict(dataaug_APA_target=0.6, dataaug_APA_p=0.0, dataaug_APA_every=4, dataaug_APA_nimg=50)
+# model_type "cut": how often dataaug_D_diffusion moves its strength (options/train_options.py:664)
+D_DIFFUSION_DEFAULTS = dict(dataaug_D_diffusion_every=4)
 
 
 def _flatten(d, prefix, out):
@@ -89,7 +91,7 @@ def opt_from_json(cfg, overrides=None, is_train=True):
         for k, v in CM_GAN_DEFAULTS.items():
             vals.setdefault(k, copy.deepcopy(v))
     if vals["model_type"] == "cut":
-        for k, v in D_AUG_DEFAULTS.items():
+        for k, v in {**D_AUG_DEFAULTS, **D_DIFFUSION_DEFAULTS}.items():
             vals.setdefault(k, v)
     opt = SimpleNamespace(**vals)
     opt.isTrain = is_train
