@@ -694,6 +694,22 @@ int jg_d_diffusion_bwd(int dtype, int nl, const void* const* dy, void* const* dx
 int jg_d_diffusion_update(float* p, int32_t* Tn, float* a, float* b, int32_t* t_epl, const float* loss, float num, float den, const float* u,
                           const uint32_t* key, uint32_t call, jg_stream_t s);
 int jg_d_diffusion_grid_cap(void);
+/* Class loss of the semantic-consistency branch (train_semantic_cls: models/base_gan_model.py:686-737, base_model.py:1497-1520), ONE launch of
+ * one workgroup on logits [B, n] with row stride ld >= n (dtype JG_F16 / JG_BF16 / JG_CLS_F32; the padding columns are never read):
+ *   loss        = lambda * gate * mean_b l_b                       (fp32 scalar)
+ *   dlogits     = lambda * gate * d l_b / d logits / B             (optional; dtype of the logits, row stride ldd >= n; padding columns untouched)
+ *   argmax[b]   = index of the row maximum, the lowest on ties     (optional; int64; 0 in the regression modes)
+ *   mode 0: cross entropy, target = int64 labels [B] (max-subtracted log-sum-exp in fp32); mode 1: MSE, mode 2: L1, target = fp32 [B], n == 1.
+ *   gate  = 1 when prev is NULL, else !(*prev > threshold) with prev an fp32 scalar in DEVICE memory (a NaN leaves the gate open); a closed
+ *           gate writes loss 0 and an all-zero gradient.
+ *   state : optional fp32 scalar in device memory that receives the loss (state_acc 0) or has it added (state_acc 1): the classifier step
+ *           records its loss there for the next iteration's gate.
+ * A label outside [0, n) is not used as an index: its row adds NaN to the loss and gets a zero gradient row.  Fixed summation order, no
+ * atomics: the same inputs give the same bits on every launch.  JG_ERR_BAD_ARG: n > 1 in a regression mode, ld / ldd < n, an unknown dtype or
+ * mode, dlogits aliasing logits. */
+#define JG_CLS_F32 2
+int jg_cls_loss(int dtype, int mode, const void* logits, int64_t ld, const void* target, int B, int n, float lambda, const float* prev,
+                float threshold, float* loss, void* dlogits, int64_t ldd, int64_t* argmax, float* state, int state_acc, jg_stream_t s);
 int jg_noise_level_embedding(const float* sigma, const float* W, float* emb, int Bn, int half, jg_stream_t s);
 /* gradient of the embedding with respect to W, ACCUMULATED into dW (the reference trains W: set_requires_grad(net, True),
  * base_model.py:1196-1217) */

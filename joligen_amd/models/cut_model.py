@@ -4,7 +4,7 @@
 :341-419, `compute_G_loss_GAN(_generic)` :421-503) for the default configuration: G_netG='resnet', D_netDs=['basic'],
 alg_cut_netF='mlp_sample', alg_cut_nce_loss in {'monce', 'patchnce', 'SRC_hDCE'}, nce_idt, lsgan, optionally the paired pixel loss
 (alg_cut_supervised_loss 'L1' / 'MSE') and the identity pixel loss (alg_cut_MSE_idt), no semantic / multimodal / context / temporal /
-augmentation branches; the discriminator regularisers dataaug_D_noise (Gaussian noise on both discriminator inputs) and dataaug_APA
+augmentation branches; the semantic-consistency class branch train_semantic_cls (a classifier as third network group, ops.cls_loss); the discriminator regularisers dataaug_D_noise (Gaussian noise on both discriminator inputs) and dataaug_APA
 (adaptive pseudo augmentation) run through ops.d_aug / ops.apa_update, dataaug_D_diffusion (Diffusion-GAN noise on the projected
 discriminator's backbone features) inside that discriminator through ops.d_diffusion / ops.d_diffusion_update.
 
@@ -23,7 +23,7 @@ from ..modules.NCE.hdce import PatchHDCELoss
 from ..modules.NCE.patchnce import MoNCELoss, PatchNCELoss
 from ..modules.cut_networks import PatchSampleF
 from ..modules.resnet_generator import ResnetGenerator
-from ..options import D_AUG_DEFAULTS
+from ..options import D_AUG_DEFAULTS, SEM_CLS_DEFAULTS
 from ..util.image_pool import ImagePool
 from .base_model import BaseModel, NetworkGroup
 from .cut_step import CUTStepDriver, gate
@@ -99,9 +99,43 @@ def check_d_aug_options(opt):
     return sigma, apa
 
 
+SEM_CLS_MODES = {"CE": ops.CLS_CE, "MSE": ops.CLS_MSE, "L1": ops.CLS_L1}      # check_sem_cls_options -> mode of ops.cls_loss
+
+
+def check_sem_cls_options(opt):
+    """train_semantic_cls (base_model.py:208-265 init_semantic_cls, semantic_networks.py:19-42 define_C) as this build accepts it: fills the
+    defaults and returns "off", or the criterion "CE" (CrossEntropyLoss), "MSE" / "L1" (train_cls_regression [+ train_cls_l1_regression]).
+    Host-only (no device).  train_sem_use_label_B, cls_class_weights, cls_all_classes_as_one and cls_dropout never reach the training step of
+    the reference (the data loader and the torchvision templates read them): accepted and ignored."""
+    for k, v in SEM_CLS_DEFAULTS.items():
+        if not hasattr(opt, k):
+            setattr(opt, k, v)
+    if not getattr(opt, "train_semantic_cls", False):
+        return "off"
+    if opt.train_sem_cls_template != "basic":
+        raise NotImplementedError(f"train_sem_cls_template={opt.train_sem_cls_template!r}: 'basic' is built (the others are torchvision models)")
+    if opt.train_sem_idt:      # base_gan_model.py:715-717 reads self.criterioncls and pred_cls_idt_B, which nothing creates
+        raise NotImplementedError("train_sem_idt with train_semantic_cls: the reference cannot run it either (its identity class term reads "
+                                  "attributes that are never set)")
+    size = int(opt.data_crop_size)
+    if size < 8 or size & (size - 1):      # classifiers.py:24-47: only a power of two reaches the 1x1 map its first Linear expects
+        raise ValueError(f"train_semantic_cls: data_crop_size={opt.data_crop_size!r} must be a power of two >= 8")
+    if opt.model_input_nc != opt.model_output_nc:
+        raise ValueError(f"train_semantic_cls: one classifier sees real_A and fake_B: model_input_nc={opt.model_input_nc!r} must equal "
+                         f"model_output_nc={opt.model_output_nc!r}")
+    n = int(getattr(opt, "cls_semantic_nclasses", 2))
+    if n < 1:
+        raise ValueError(f"cls_semantic_nclasses={n!r}: >= 1 is required")
+    if opt.train_cls_regression and n != 1:
+        raise ValueError(f"train_cls_regression predicts one value per image: cls_semantic_nclasses={n!r} must be 1")
+    if not opt.train_cls_regression:
+        return "CE"
+    return "L1" if opt.train_cls_l1_regression else "MSE"
+
+
 def cut_loss_names(opt, discriminators_names):
     """loss_names of the generator group in the reference's order (cut_model.py:444-455): G_tot, G_NCE, [G_supervised], [G_NCE_Y], [G_MSE_idt],
-    G_GAN_*.  Host-only (no device)."""
+    G_GAN_*, [G_sem_cls_AB] (base_model.py:212-224, appended last).  Host-only (no device)."""
     names = ["G_tot", "G_NCE"]
     if [s for s in getattr(opt, "alg_cut_supervised_loss", [""]) if s]:
         names.append("G_supervised")
@@ -109,7 +143,20 @@ def cut_loss_names(opt, discriminators_names):
         names.append("G_NCE_Y")
     if getattr(opt, "alg_cut_MSE_idt", False):
         names.append("G_MSE_idt")
-    return names + ["G_GAN_" + dn for dn in discriminators_names]
+    names += ["G_GAN_" + dn for dn in discriminators_names]
+    if getattr(opt, "train_semantic_cls", False):
+        names.append("G_sem_cls_AB")
+    return names
+
+
+def cut_all_loss_names(opt, discriminators_names):
+    """loss_names of the model in the reference's order: the generator's, the discriminators', then with train_semantic_cls G_sem_cls_AB and
+    CLS (cut_model.py:479 joins G and D before base_model.py:224-226 appends the class names to loss_names_G and to loss_names: the two come
+    AFTER the discriminators' names here, G_sem_cls_AB last in loss_names_G).  Host-only (no device)."""
+    names = [n for n in cut_loss_names(opt, discriminators_names) if n != "G_sem_cls_AB"] + ["D_tot"] + ["D_GAN_" + dn for dn in discriminators_names]
+    if getattr(opt, "train_semantic_cls", False):
+        names += ["G_sem_cls_AB", "CLS"]
+    return names
 
 
 class CUTModel(BaseModel):
@@ -133,11 +180,11 @@ class CUTModel(BaseModel):
             raise NotImplementedError(f"alg_cut_netF={opt.alg_cut_netF!r}")
         self.hdce = check_nce_options(opt)
         self.pixel_modes = check_pixel_loss_options(opt)      # (supervised term, identity term) of ops.pixel_loss
-        for flag in ("model_multimodal", "alg_cut_flip_equivariance", "train_semantic_mask", "train_semantic_cls",
-                     "train_mask_out_mask"):
+        for flag in ("model_multimodal", "alg_cut_flip_equivariance", "train_semantic_mask", "train_mask_out_mask"):
             if getattr(opt, flag, False):
                 raise NotImplementedError(f"{flag} is outside the SURVEY.md 8 hot path")
         check_d_aug_options(opt)
+        self.sem_cls = check_sem_cls_options(opt)      # "off" | "CE" | "MSE" | "L1"
         # dataaug_D_diffusion: the projected discriminator noises its own backbone features (modules/projected_d.Diffusion) and its loss
         # calculator moves the strength; nothing of it lives in this model
         self.d_diffusion = check_d_diffusion_options(opt)
@@ -198,8 +245,10 @@ class CUTModel(BaseModel):
             self.networks_groups = [self.group_G, self.group_D]
             self.loss_names_G = cut_loss_names(opt, self.discriminators_names)
             self.loss_names_D = ["D_tot"] + ["D_GAN_" + dn for dn in self.discriminators_names]
-            self.loss_names = self.loss_names_G + self.loss_names_D
+            self.loss_names = cut_all_loss_names(opt, self.discriminators_names)
             self.loss_functions_G = ["compute_G_loss_GAN", "compute_G_loss_cut"]
+            if self.sem_cls != "off":
+                self.init_semantic_cls(opt, kw)
             self.iter_calculator_init()
         else:
             self.netG_A.jg_finalize(self.device, self.act_dtype)
@@ -211,6 +260,82 @@ class CUTModel(BaseModel):
         if self.d_apa and opt.isTrain:
             self.visual_names.append(["APA_img"])
 
+    # ---- semantic-consistency class branch (train_semantic_cls) -------------------------------------------------------------------------
+    def init_semantic_cls(self, opt, kw):
+        """base_model.py:208-265: netCLS, its criterion and optimizer, and the third network group [G, D, CLS]."""
+        from ..modules.classifier import Classifier
+
+        self.netCLS = Classifier(opt.model_output_nc, opt.cls_nf, opt.cls_semantic_nclasses, opt.data_crop_size, init_type=opt.model_init_type,
+                                 init_gain=opt.model_init_gain)
+        self.model_names += ["CLS"]
+        self.loss_names_CLS = ["CLS"]
+        # base_model.py:237-244: the reference builds this optimizer with train_sem_lr_f_s -- train_sem_lr_cls is never read.  Its slip, mirrored.
+        self.optimizer_CLS = self.make_optimizer(self.netCLS, **{**kw, "lr": opt.train_sem_lr_f_s})
+        self.optimizers.append(self.optimizer_CLS)
+        self.group_CLS = NetworkGroup(networks_to_optimize=["CLS"], forward_functions=None, backward_functions=["compute_CLS_loss"],
+                                      loss_names_list=["loss_names_CLS"], optimizer=["optimizer_CLS"], loss_backward=["loss_CLS"])
+        self.networks_groups.append(self.group_CLS)
+        self.loss_functions_G.insert(1, "compute_G_loss_semantic_cls")      # base_gan_model.py:151-153, cut_model.py:499: GAN, class, CUT
+        # the gate of the generator's class term (base_gan_model.py:719-724) reads LAST iteration's loss_CLS: kept as a device scalar that the
+        # classifier step's loss launch writes and the generator's launch reads -- no host synchronisation.  +inf = "no loss_CLS yet": closed.
+        self.loss_CLS_prev = torch.full((), float("inf"), device=self.device, dtype=torch.float32)
+
+    def sem_cls_gate_open(self):
+        """whether the NEXT generator step's class term is let through (a host read of the device scalar: logging and tests only)"""
+        return not float(self.loss_CLS_prev) > float(self.opt.f_s_semantic_threshold)
+
+    def _set_input_semantic_cls(self, data):
+        """base_model.py:476-494: A_label_cls (long; float in regression mode) and, if present, B_label_cls.  The range check runs here, where
+        the labels are still on the host: the kernel turns a bad label into a NaN loss, this turns it into an error."""
+        regression = self.sem_cls != "CE"
+        n = int(self.opt.cls_semantic_nclasses)
+        for dom in ("A", "B"):
+            key = dom + "_label_cls"
+            if key not in data:
+                if dom == "A" or self.opt.train_sem_cls_B:
+                    raise KeyError(f"train_semantic_cls{' with train_sem_cls_B' if dom == 'B' else ''} needs data[{key!r}]")
+                continue
+            lab = torch.as_tensor(data[key]).reshape(-1)
+            if not regression and not lab.is_cuda and lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= n):
+                raise ValueError(f"{key} holds a class outside [0, {n}): {lab.tolist()}")
+            lab = lab.to(torch.float32 if regression else torch.int64)
+            setattr(self, f"input_{dom}_label_cls", lab.to(self.device, non_blocking=True).contiguous())
+
+    def forward_semantic_cls(self):
+        """base_model.py:1618-1635: netCLS(real_A) then netCLS(fake_B), both in train mode: each pass normalises with its batch statistics and
+        updates the running ones (the third pass of the iteration is compute_CLS_loss).  The argmaxes of the reference (gt_pred_cls_A / pfB)
+        come out of the loss launches on the same logits: pfB from the generator's term, gt_pred_cls_A from the classifier's (its pass on
+        real_A sees the same weights and batch statistics as this one)."""
+        net = self._net("CLS")
+        self.pred_cls_real_A = net(self.real_A)
+        self.pred_cls_fake_B = net(self.fake_B)
+
+    def compute_G_loss_semantic_cls(self):
+        """base_gan_model.py:686-737: lambda * gate * criterion(netCLS(fake_B), label_A); the gate reads f_s_semantic_threshold (the reference's
+        slip: cls_semantic_threshold is never read; mirrored) against last iteration's loss_CLS on the device."""
+        o = self.opt
+        self.loss_G_sem_cls_AB, self.pfB = ops.cls_loss(self.pred_cls_fake_B, self.input_A_label_cls, SEM_CLS_MODES[self.sem_cls], o.train_sem_cls_lambda,
+                                                        prev=self.loss_CLS_prev, threshold=o.f_s_semantic_threshold)
+        self.loss_G_tot = self.loss_G_tot + self.loss_G_sem_cls_AB
+
+    def compute_CLS_loss(self):
+        """base_model.py:1497-1520: lambda * criterion(netCLS(real_A), label_A) [+ the same on real_B with train_sem_cls_B], ungated; the
+        launch(es) leave the value in loss_CLS_prev for the next iteration's gate."""
+        o = self.opt
+        net, mode = self._net("CLS"), SEM_CLS_MODES[self.sem_cls]
+        loss, self.gt_pred_cls_A = ops.cls_loss(net(self.real_A), self.input_A_label_cls, mode, o.train_sem_cls_lambda, state=self.loss_CLS_prev)
+        if o.train_sem_cls_B:
+            loss_B, self.gt_pred_cls_B = ops.cls_loss(net(self.real_B), self.input_B_label_cls, mode, o.train_sem_cls_lambda, state=self.loss_CLS_prev,
+                                                      state_acc=True)
+            loss = loss + loss_B
+        self.loss_CLS = _ScaleGradFn.apply(loss, self.loss_scale)
+
+    def parallelize(self, rank):
+        if self.sem_cls != "off" and len(self.opt.gpu_ids) > 1:
+            raise NotImplementedError("train_semantic_cls on more than one GPU: the classifier's synchronised BatchNorm statistics over its three "
+                                      "passes and a third arena in the gradient exchange are not built")
+        super().parallelize(rank)
+
     # ---- inputs ---------------------------------------------------------------------------------------------------
     def set_input(self, data):
         self.real_A_nchw = data["A"].to(self.device, non_blocking=True)
@@ -218,6 +343,8 @@ class CUTModel(BaseModel):
         self.real_A = ops.to_nhwc(self.real_A_nchw, self.act_dtype)
         self.real_B = ops.to_nhwc(self.real_B_nchw, self.act_dtype)
         self.batch_size = self.real_A.shape[0]
+        if self.sem_cls != "off" and self.opt.isTrain:
+            self._set_input_semantic_cls(data)
 
     def get_current_batch_size(self):
         return self.batch_size
@@ -245,6 +372,8 @@ class CUTModel(BaseModel):
             self.real_A_pool.store(self.real_A)
             self.real_B_pool.store(self.real_B)
         self._forward_core()
+        if self.sem_cls != "off" and self.opt.isTrain:
+            self.forward_semantic_cls()
 
     def _reuse_feats(self):
         """`jg_nce_reuse_feats` (round 6, default on): the key-side features of both contrastive terms -- `netG.get_feats` of the source image
@@ -449,6 +578,8 @@ class CUTModel(BaseModel):
     def optimize_parameters(self):
         if not self.driver.early_D():
             self.step_driver = "sequential"
+            if self.sem_cls != "off" and self.opt.isTrain:      # three groups: the early-D and captured drivers are built for [G, D]
+                self.step_driver_note = "train_semantic_cls: the CLS group is a third network group; the step runs the groups in sequence"
             return super().optimize_parameters()
         self.driver.optimize_parameters()
 

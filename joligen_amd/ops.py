@@ -1900,6 +1900,83 @@ def pixel_loss(x, y, C, modes, lambdas):
     return _PixelLossFn.apply(x, y.detach(), int(C), modes, lambdas)
 
 
+# ---- class loss of the semantic-consistency branch (train_semantic_cls; csrc/sem_cls.hip) -------------------------------------------------
+CLS_CE, CLS_MSE, CLS_L1 = 0, 1, 2              # modes of jg_cls_loss
+_CLS_DT = {torch.float16: _lib.JG_F16, torch.bfloat16: _lib.JG_BF16, torch.float32: 2}      # 2: JG_CLS_F32 of include/jg355.h
+
+
+def _cls_loss_check(logits, target, mode, prev, state):
+    """the argument checks of jg_cls_loss, before any launch (ValueError); returns (B, n, row stride)"""
+    if int(mode) not in (CLS_CE, CLS_MSE, CLS_L1):
+        raise ValueError(f"cls_loss: mode {mode!r} is not 0 (cross entropy), 1 (MSE) or 2 (L1)")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"cls_loss: logits {tuple(logits.shape)} are not [B, n]")
+    B, n = logits.shape
+    if logits.dtype not in _CLS_DT:
+        raise ValueError(f"cls_loss: logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < n):
+        raise ValueError(f"cls_loss: the rows of the logits must be contiguous (strides {tuple(logits.stride())})")
+    if mode != CLS_CE and n != 1:
+        raise ValueError(f"cls_loss: the regression modes take one value per sample, got n = {n}")
+    want = torch.int64 if mode == CLS_CE else torch.float32
+    if target.dtype != want or target.numel() != B or not target.is_contiguous():
+        raise ValueError(f"cls_loss: target must be contiguous {want} with {B} entries, got {target.dtype} {tuple(target.shape)}")
+    for name, t in (("prev", prev), ("state", state)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1):
+            raise ValueError(f"cls_loss: {name} must be one float32 value in device memory")
+    return B, n, (logits.stride(0) if B > 1 else max(n, logits.stride(0)))
+
+
+def _cls_loss_launch(logits, target, mode, lam, prev, threshold, state, state_acc):
+    """(loss fp32 scalar, dlogits [B, n] for a unit upstream gradient, argmax int64 [B]) of jg_cls_loss: one launch"""
+    B, n, ld = _cls_loss_check(logits, target, mode, prev, state)
+    _require_cuda(logits, target, prev, state)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty((B, n), device=logits.device, dtype=logits.dtype)
+    argmax = torch.empty(B, device=logits.device, dtype=torch.int64)
+    check(_lib.lib().jg_cls_loss(_CLS_DT[logits.dtype], int(mode), logits.data_ptr(), ld, target.data_ptr(), B, n, float(lam), _p(prev), float(threshold),
+                                 loss.data_ptr(), dlogits.data_ptr(), n, argmax.data_ptr(), _p(state), int(bool(state_acc)), _st()), "jg_cls_loss")
+    return loss, dlogits, argmax
+
+
+def _cls_loss_scale(dlogits, gout):
+    """the saved unit gradient times the incoming scalar, read on the device"""
+    g = gout.contiguous().float()
+    if dlogits.dtype == torch.float32 or dlogits.numel() % 8:      # jg_axpby walks 16-bit data in groups of 8
+        return (dlogits.float() * g).to(dlogits.dtype)
+    return axpby(dlogits, 1.0, alpha_dev=g)
+
+
+class _ClsLossFn(JGFunction):
+    @staticmethod
+    def forward(ctx, logits, target, mode, lam, prev, threshold, state, state_acc):
+        loss, dlogits, argmax = _cls_loss_launch(logits, target, mode, lam, prev, threshold, state, state_acc)
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(argmax)
+        return loss, argmax
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout, _gargmax):
+        (dlogits,) = ctx.saved_tensors
+        return (_cls_loss_scale(dlogits, gout),) + (None,) * 7
+
+
+def cls_loss(logits, target, mode=CLS_CE, lam=1.0, prev=None, threshold=1.0, state=None, state_acc=False):
+    """The class loss of train_semantic_cls on logits [B, n] (fp32 or 16-bit; a row stride above n is allowed, the padding is not read):
+    lam * gate * CrossEntropyLoss (mode CLS_CE, int64 labels) / MSELoss / L1Loss (CLS_MSE / CLS_L1, fp32 targets, n == 1), with
+    gate = !(prev > threshold) read on the device (`prev`: fp32 device scalar; None: no gate), plus the per-row argmax (int64, lowest index on
+    ties).  `state` (fp32 device scalar) receives the loss, or has it added with state_acc.  Returns (loss, argmax); loss, gradient and
+    argmax come from one launch (jg_cls_loss), the backward scales the saved gradient by the incoming scalar."""
+    args = (logits, target.detach(), int(mode), float(lam), prev, float(threshold), state, bool(state_acc))
+    if TORCH_OPS_BOUNDARY:
+        out = torch.ops.jg355.cls_loss(*args[:6])
+        if state is not None:      # the functional op cannot write the gate state: one small device-side copy instead
+            state.add_(out[0].detach()) if state_acc else state.copy_(out[0].detach())
+        return out[0], out[2]
+    return _ClsLossFn.apply(*args)
+
+
 # ---- discriminator-input augmentations: dataaug_D_noise and adaptive pseudo augmentation (csrc/d_aug.hip) ----------------------------------
 D_AUG_MAX = 4                  # targets of one jg_d_aug launch (JG_D_AUG_MAX of include/jg355.h)
 D_AUG_NOISE_STREAM = 0         # Philox stream id of the noise; the flags of target d draw on stream 1 + d unless the caller says otherwise

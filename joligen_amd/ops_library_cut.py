@@ -17,6 +17,7 @@ tests/test_gpu_5_cutloss.py::test_cut_step_through_torch_ops holds the two forms
   gather_patches / scatter_patches, l2_normalize / _bwd, patch_nce / patch_nce_bwd      PatchSampleF + PatchNCE / MoNCE (Sinkhorn inside)
   patch_hdce / patch_hdce_bwd                SRC_hDCE: weights from the key Gram matrix + weighted contrastive loss, one fused kernel
   pixel_loss / pixel_loss_bwd                paired (supervised) and identity L1 / MSE between 16-bit images, both terms in one launch set
+  cls_loss                                   train_semantic_cls: cross entropy / MSE / L1 with the device-side gate, gradient and argmax, one launch
   d_aug, apa_update                          dataaug_D_noise + adaptive pseudo augmentation: the discriminators' inputs of a step; the update of p
   d_diffusion / _bwd, d_diffusion_update     dataaug_D_diffusion: the noised backbone features of the projected discriminator; the update of its state
   gan_loss, hinge_loss                       GANLoss (lsgan / vanilla / wgangp) and the projected hinge; return (loss, d loss / d pred)
@@ -690,6 +691,35 @@ def _pl_backward(ctx, g):
 
 
 pixel_loss.register_autograd(_pl_backward, setup_context=_pl_setup)
+
+
+# ---- class loss of the semantic-consistency branch ------------------------------------------------------------------------------------
+@op("jg355::cls_loss", mutates_args=())
+def cls_loss(logits: T, target: T, mode: int, lam: float, prev: Optional[T], threshold: float) -> Tuple[T, T, T]:
+    """ops.cls_loss as a functional op: -> (loss fp32 scalar, d loss / d logits [B, n] for a unit upstream gradient, argmax int64 [B]); mode 0
+    cross entropy (int64 labels), 1 MSE, 2 L1 (fp32 targets, n == 1); gate = !(prev > threshold) on the device.  The gate state that the
+    C entry point can write in the same launch is an in-place update: a functional op leaves it to the caller"""
+    return ops._cls_loss_launch(logits, target, mode, lam, prev, threshold, None, False)
+
+
+@cls_loss.register_fake
+def _(logits, target, mode, lam, prev, threshold):
+    B, n = logits.shape
+    return logits.new_empty((), dtype=torch.float32), logits.new_empty((B, n)), logits.new_empty((B,), dtype=torch.int64)
+
+
+def _cls_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _cls_backward(ctx, gloss, gd, gargmax):
+    (dlogits,) = ctx.saved_tensors
+    g = None if gloss is None else ops._cls_loss_scale(dlogits, gloss)
+    return (g,) + (None,) * 5
+
+
+cls_loss.register_autograd(_cls_backward, setup_context=_cls_setup)
 
 
 # ---- discriminator-input augmentations (not differentiable: the reference detaches their inputs) -----------------------------------------

@@ -65,6 +65,17 @@ D_AUG_DEFAULTS = dict(dataaug_APA_target=0.6, dataaug_APA_p=0.0, dataaug_APA_eve
 D_DIFFUSION_DEFAULTS = dict(dataaug_D_diffusion_every=4)
 
 
+# model_type "cut": the class branch of train_semantic_cls (options/common_options.py cls_*, f_s_semantic_threshold; options/train_options.py
+# train_sem_*, train_cls_*); cut_model.check_sem_cls_options fills and checks them
+SEM_CLS_DEFAULTS = dict(
+    cls_nf=64, f_s_semantic_threshold=1.0, train_sem_cls_lambda=1.0, train_sem_lr_f_s=2e-4, train_sem_cls_template="basic",
+    train_sem_cls_B=False, train_sem_cls_pretrained=False, train_cls_regression=False, train_cls_l1_regression=False, train_sem_idt=False,
+    train_sem_net_output=False, train_sem_use_label_B=False,
+)
+# options/common_options.py:208-210: the generator of the GAN models when a config names none (DEFAULTS holds the palette model's)
+CUT_DEFAULT_NETG = "mobile_resnet_attn"
+
+
 def _flatten(d, prefix, out):
     for k, v in d.items():
         key = f"{prefix}_{k}" if prefix else k
@@ -93,6 +104,8 @@ def opt_from_json(cfg, overrides=None, is_train=True):
     if vals["model_type"] == "cut":
         for k, v in {**D_AUG_DEFAULTS, **D_DIFFUSION_DEFAULTS}.items():
             vals.setdefault(k, v)
+        if "G_netG" not in flat and "G_netG" not in (overrides or {}):
+            vals["G_netG"] = CUT_DEFAULT_NETG
     opt = SimpleNamespace(**vals)
     opt.isTrain = is_train
     # options/common_options.py:1100-1108: "0,1" -> [0, 1]; "-1" -> []
