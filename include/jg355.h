@@ -32,13 +32,10 @@ enum { JG_OUT_ATOMIC_F32 = 0, JG_OUT_STORE_F32 = 1, JG_OUT_STORE_T = 2 };
 int jg_version(void);
 const char* jg_strerror(int code);
 
-/* Dispatch switches.  Each switch is read once from the environment variable of the same name
- * ("JG_HALO_CFG", "JG_WGRAD_HALO_CFG", "JG_CONV_VARIANT", "JG_WGRAD_VARIANT", "JG_SINKHORN_GENERIC", "JG_CONV1X1",
- * "JG_GN_REVERSE", "JG_HALO_DBG", "JG_PERSIST64", "JG_HALO_PIPE", "JG_WGRAD_PIPE", "JG_CONV_SPLITK", "JG_CONV_SMALL_TILE",
- * "JG_GN_FUSED", "JG_GN_FUSED_CAP", "JG_GN_FUSED_DBG", "JG_GN_FUSED_SLEEP", "JG_WGRAD_LDS_PAD", and the grid shapes of the SegFormer
- * backward kernels "JG_LN_BWD_CAP" (256 workgroups), "JG_DW_BWD_CAP" (512) and "JG_DW_BWD_PPT" (8 pixels per thread));
- * jg_set_tuning overrides it for the rest of the process (parity tests use
- * it to force a tile configuration that the automatic choice only takes at bench-sized grids).  No reference counterpart:
+/* Dispatch switches.  Each switch is read once from the environment variable of the same name ("JG_HALO_CFG",
+ * "JG_CONV_VARIANT", ...; the one list of names and defaults is JG_TUNE_LIST in joligen_amd/csrc/common.h); jg_set_tuning overrides it
+ * for the rest of the process (parity tests use it to force a tile configuration that the automatic choice only takes at bench-sized
+ * grids).  No reference counterpart:
  * the reference delegates kernel choice to cuDNN's heuristics (torch.backends.cudnn.benchmark, train.py:38-48).
  * Returns JG_OK / JG_ERR_BAD_ARG (unknown name); jg_get_tuning returns the current value or -1. */
 int jg_set_tuning(const char* name, int value);
@@ -593,7 +590,7 @@ int jg_ddpm_p_sample(int dtype, float* y_t, const float* y_cond, const void* noi
  *                dFn = grad_scale * lambda/B * d / (sqrt(S_b + c^2) * dt[b]) * m * co_n[b] (0 in the pad channels and where m == 0).
  *                Two launches on `s`: per-block partial sums of d^2 into `ws`, then the gradient and the scalar.  No atomics and
  *                nothing to zero: loss and dFn are overwritten and are the same bits on every run.  `ws` is the caller's, at least
- *                B * min(ceil(H*W / 256), 64) floats (`ws_floats` says how many it holds).  Cpad must be 8 (one 16-byte access per
+ *                B * min(ceil(H*W / 256), JG_ECT_MAX_BLOCKS) floats (`ws_floats` says how many it holds).  Cpad must be 8 (one 16-byte access per
  *                pixel; JG_ERR_UNSUPPORTED otherwise) and Fn, Fc, dFn 16-byte aligned.
  *   noise_level_embedding : [sin | cos](sigma * W * 2 pi)  (NoiseLevelEmbedding.forward :276-280) */
 int jg_cm_noisy(int dtype, const float* x, const float* noise, const float* sigma, const int64_t* mask, const float* cond,
@@ -618,6 +615,7 @@ int jg_cm_gan_head(int dtype, const void* Fn, const void* Fc, const float* noisy
                    jg_stream_t s);
 int jg_cm_gan_head_bwd(int dtype, const void* dFn_cm, const void* dpred, const float* g_loss, const float* co_n, void* dF, int B, int C,
                        int H, int W, int Cpad, jg_stream_t s);
+#define JG_ECT_MAX_BLOCKS 64
 int jg_ect_loss(int dtype, const void* Fn, const void* Fc, const float* noisy_n, const float* noisy_c, const float* cs_n,
                 const float* co_n, const float* cs_c, const float* co_c, const int64_t* mask, const float* dt, float* ws,
                 int64_t ws_floats, float* loss, void* dFn, int B, int C, int H, int W, int Cpad, float c, float lambda,
@@ -628,12 +626,13 @@ int jg_ect_loss(int dtype, const void* Fn, const void* Fc, const float* noisy_n,
  *   an off segment yields exactly 0.  The pad channels may hold anything (NaN included).
  *   jg_pixel_loss     : two launches on `s`: per-block partial sums into `ws`, then each segment's partials added in index order.  No
  *                       atomics, nothing to zero: the same bits on every run.  `ws` is the caller's, at least
- *                       S * min(ceil(M*H*W / 256), 256) floats (`ws_floats` says how many it holds).
+ *                       S * min(ceil(M*H*W / 256), JG_PIXEL_MAX_BLOCKS) floats (`ws_floats` says how many it holds).
  *   jg_pixel_loss_bwd : dx = g[s] * lambda_s / (M*C*H*W) * (sign(d) | 2 d), d recomputed, g a DEVICE vector of S upstream gradients
  *                       (no host read: capturable); formed in fp32, rounded once; 0 in the pad channels, where d == 0 under L1 and
  *                       everywhere in an off segment.
  *   Cpad must be 8 (one 16-byte access per pixel; JG_ERR_UNSUPPORTED otherwise); x, y, dx 16-byte aligned, S in 1..2 and the modes in
  *   0..2 (JG_ERR_BAD_ARG otherwise). */
+#define JG_PIXEL_MAX_BLOCKS 256
 int jg_pixel_loss(int dtype, const void* x, const void* y, float* ws, int64_t ws_floats, float* loss, int S, int M, int C, int H, int W,
                   int Cpad, int mode0, int mode1, float lambda0, float lambda1, jg_stream_t s);
 int jg_pixel_loss_bwd(int dtype, const void* x, const void* y, const float* g, void* dx, int S, int M, int C, int H, int W, int Cpad,
@@ -742,9 +741,10 @@ int jg_resize_nearest_u8(const uint8_t* in, uint8_t* out, const int32_t* ytab, c
  * up along H, up along W), per pass: first source index int32 [n_out], tap count int32 [n_out], normalised fp32 taps [n_out][K] --
  * K = Kdown for both down passes (the wider axis' 2 ceil(n_in / n_out) + 1; rows of the narrower one zero-padded), K = 3 for the up
  * passes -- computed as ATen computes them (joligen_amd/resize_aa.py).  No atomics: bit-identical from run to run.
- * JG_ERR_UNSUPPORTED: Kdown above 65 taps, or no band of output rows whose input rows fit the 160 KiB of LDS (every ratio in [1, 8] up
+ * JG_ERR_UNSUPPORTED: Kdown above JG_LOWRES_MAX_TAPS taps, or no band of output rows whose input rows fit the 160 KiB of LDS (every ratio in [1, 8] up
  * to 512 x 512 fits).  jg_lowres_roundtrip_band: the rows of output one workgroup produces for that shape (> 0), or the same error
  * codes -- the support probe, no launch. */
+#define JG_LOWRES_MAX_TAPS 65
 int jg_lowres_roundtrip_f32(const float* x, float* y, const int32_t* dh_min, const int32_t* dh_size, const float* dh_w, const int32_t* dw_min,
                             const int32_t* dw_size, const float* dw_w, const int32_t* uh_min, const int32_t* uh_size, const float* uh_w,
                             const int32_t* uw_min, const int32_t* uw_size, const float* uw_w, int planes, int H, int W, int Hlo, int Wlo,

@@ -1,18 +1,21 @@
 """ctypes binding of libjg355.so (the C ABI declared in include/jg355.h).
 
-The library is built in-tree with hipcc for gfx950 (`build()`), loaded once, and every entry
-point gets its argtypes from the table below.  There is NO fallback: if the shared object is
-missing or a symbol is absent, importing the ops fails loudly.
+The library is built in-tree with hipcc for gfx950 (`build()`) and loaded once.  The header is the single statement of the ABI: it is
+parsed at import, and the argtypes / restype of every entry point, the ctypes mirrors of its structs and every JG_* constant come from
+it.  There is NO fallback: if the shared object is missing or a symbol is absent, importing the ops fails loudly, and a declaration the
+parser does not understand is an error, never a guess.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libjg355.so")
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "jg355.h")
 SOURCES = ["attention.hip", "gemm_nt.hip", "conv_halo.hip", "conv_kxk.hip", "reflect_border.hip", "conv_p64.hip", "conv1x1.hip", "gemm_tn.hip", "wgrad_halo.hip", "wgrad_sw.hip", "wgrad_kxk.hip", "nce.hip", "segformer.hip", "vit.hip", "projected_d.hip", "effnet.hip", "norm.hip", "gn_fused.hip", "elementwise.hip", "d_aug.hip", "d_diffusion.hip", "sem_cls.hip", "resize_aa.hip", "optim.hip", "capi.hip"]
 # -fno-slp-vectorize: the SLP vectoriser packs independent fp32 chains into v_pk_* pairs (register tuples: gn_fused.hip went from 150 spilled
 # registers to none without it) -- "an anti-lever beside MFMAs" in the MI355X guide; same-box A/B of the whole step: 52.2 -> 52.0 ms
@@ -20,201 +23,77 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 
 FILE_FLAGS = {}      # per-source extra flags
 
-JG_OK, JG_ERR_BAD_ARG, JG_ERR_UNSUPPORTED, JG_ERR_LAUNCH = 0, -1, -2, -3
-JG_F16, JG_BF16 = 0, 1
-JG_ACT_NONE, JG_ACT_SILU, JG_ACT_RELU, JG_ACT_LRELU, JG_ACT_TANH = 0, 1, 2, 3, 4
-JG_OUT_ATOMIC_F32, JG_OUT_STORE_F32, JG_OUT_STORE_T = 0, 1, 2
-
 c_i32, c_i64, c_f32, c_p = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
-
-class ConvArgs(C.Structure):
-    _fields_ = (
-        [(n, c_p) for n in ("x", "w", "y", "bias", "res")]
-        + [(n, c_i32) for n in ("B", "H", "W", "Cin", "Cout", "R", "S", "pad", "stride", "Ho", "Wo")]
-        + [(n, c_i64) for n in ("ldx", "ldw", "ldy", "ldres")]
-        + [(n, c_i32) for n in ("nbatch", "nh")]
-        + [(n, c_i64) for n in ("sxb", "sxh", "swb", "swh", "syb", "syh", "srb", "srh")]
-        + [("alpha", c_f32), ("res_scale", c_f32), ("out_f32", c_i32), ("stats", c_p), ("ldstats", c_i64), ("stats_slots", c_i32), ("stats_mode", c_i32), ("gn_x", c_p), ("gn_ldx", c_i64), ("gn_ab", c_p), ("gn_act", c_i32), ("pad_mode", c_i32), ("res_mode", c_i32), ("x_mode", c_i32), ("y_mode", c_i32), ("ws", c_p), ("ws_bytes", c_i64)]
-    )
+_SCALARS = {"int": c_i32, "int32_t": c_i32, "int64_t": c_i64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": c_f32, "jg_stream_t": c_p}
 
 
-class WgradArgs(C.Structure):
-    _fields_ = (
-        [(n, c_p) for n in ("dy", "x", "dw", "dbias")]
-        + [(n, c_i32) for n in ("B", "H", "W", "Cin", "Cout", "R", "S", "pad", "stride", "Ho", "Wo")]
-        + [(n, c_i32) for n in ("Cin_out", "Cout_out")]
-        + [(n, c_i64) for n in ("lddy", "ldx", "lddw")]
-        + [(n, c_i32) for n in ("nbatch", "nh", "splitk")]
-        + [(n, c_i64) for n in ("sdyb", "sdyh", "sxb", "sxh", "sdwb", "sdwh")]
-        + [("alpha", c_f32), ("out_mode", c_i32), ("dbias_scale", c_f32), ("pad_mode", c_i32), ("x_mode", c_i32)]
-    )
+def _ctype(decl: str, structs: dict, where: str):
+    """ctypes type of the declaration `type [name]`; the closed type map of the ABI, anything else raises"""
+    tok = re.findall(r"\w+|\*", decl)
+    if len(tok) > 1 and tok[-1] != "*":
+        tok = tok[:-1]          # the parameter / field name
+    if not tok or re.sub(r"[\w\s*]", "", decl):
+        raise TypeError(f"jg355.h: cannot parse `{decl.strip()}` in `{where}`")
+    if "*" not in tok:
+        if len(tok) == 1 and tok[0] in _SCALARS:
+            return _SCALARS[tok[0]]
+        raise TypeError(f"jg355.h: type `{' '.join(tok)}` of `{decl.strip()}` in `{where}` is outside the ABI's type map")
+    if tok == ["const", "char", "*"]:
+        return C.c_char_p
+    if len(tok) == 3 and tok[0] == "const" and tok[1] in structs and tok[2] == "*":
+        return C.POINTER(structs[tok[1]])
+    return c_p
 
 
-# name -> argtypes (restype is int except where noted); mirrors include/jg355.h one to one
-SIGNATURES = {
-    "jg_version": [],
-    "jg_strerror": [c_i32],
-    "jg_set_tuning": [C.c_char_p, c_i32],
-    "jg_get_tuning": [C.c_char_p],
-    "jg_last_kernel": [],
-    "jg_conv2d_nt": [c_i32, C.POINTER(ConvArgs), c_p],
-    "jg_conv1x1_gn_apply": [c_i32, C.POINTER(ConvArgs), c_p, c_p, c_i64, c_i32, c_p],
-    "jg_conv1x1_gn_bwd_apply": [c_i32, C.POINTER(ConvArgs), c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_f32, c_p, c_i64, c_f32, c_i32, c_p],
-    "jg_conv2d_wgrad_tn": [c_i32, C.POINTER(WgradArgs), c_p],
-    "jg_conv2d_wgrad_tn_group": [c_i32, C.POINTER(WgradArgs), c_i32, c_p],
-    "jg_gn_stats": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_coef": [c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_gn_apply": [c_i32, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_apply_add": [c_i32, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_reduce": [c_i32, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_subpixel_fold": [c_i32, c_p, c_p, c_i32, c_i32, c_p],
-    "jg_transposed_fold": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_apply_pool": [c_i32, c_p, c_i64, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_gn_bwd_reduce_up": [c_i32, c_p, c_i64, c_p, c_i64, c_f32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_reduce_up_acc": [c_i32, c_p, c_i64, c_p, c_i64, c_f32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_fused": [c_i32, c_i32, c_p, c_i64, c_p, c_i64, c_f32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p, c_i64,
-                        c_p, c_i64, c_f32, c_p, c_i64, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_apply_fc": [c_i32, c_i32, c_p, c_i64, c_p, c_i64, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p, c_i64,
-                           c_p, c_i64, c_f32, c_p, c_i64, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_reduce_ld_acc": [c_i32, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_apply_up": [c_i32, c_p, c_i64, c_p, c_i64, c_f32, c_p, c_p, c_p, c_i64, c_p, c_i64, c_f32, c_p, c_i64, c_f32, c_i32, c_i32,
-                           c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_coef": [c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_coef_slots": [c_p, c_i32, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_apply": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_stats_ld": [c_i32, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_coef_ld": [c_p, c_i64, c_i32, c_p, c_p, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_gn_apply_ld": [c_i32, c_p, c_i64, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_reduce_ld": [c_i32, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gn_bwd_apply_ld": [c_i32, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_f32, c_p, c_i64, c_f32,
-                           c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_pool2x2": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_upsample2x": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_pool2x2_ld": [c_i32, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_upsample2x_ld": [c_i32, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_copy_channels": [c_i32, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_i32, c_p],
-    "jg_axpby": [c_i32, c_p, c_f32, c_p, c_p, c_f32, c_p, c_i64, c_p],
-    "jg_transpose_heads": [c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_softmax_fwd": [c_i32, c_p, c_p, c_i64, c_i32, c_p],
-    "jg_softmax_bwd": [c_i32, c_p, c_p, c_p, c_i64, c_i32, c_f32, c_p],
-    "jg_attention_fwd": [c_i32, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_attention_bwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_linear_fwd": [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_linear_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_gamma_embedding": [c_p, c_p, c_i32, c_i32, c_f32, c_p],
-    "jg_ddpm_prepare": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_ddpm_mse_loss": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_p],
-    "jg_act_fwd": [c_i32, c_p, c_p, c_i64, c_i32, c_p],
-    "jg_act_bwd": [c_i32, c_p, c_p, c_p, c_i64, c_i32, c_p],
-    "jg_reflect_pad2d": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_crop2d": [c_i32, c_p, c_p] + [c_i32] * 9 + [c_p],
-    "jg_reflect_pad2d_bwd": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_reflect_dgrad_border": [c_i32, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_reflect_dgrad_border_ws_floats": [c_i32, c_i32, c_i32, c_i32],
-    "jg_dilate2d": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_tapsum7": [c_i32, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_tapspread7": [c_i32, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_conv_dgrad_gather": [c_i32, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_subsample2d": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_channel_sum": [c_i32, c_p, c_i64, c_p, c_i64, c_i32, c_f32, c_p],
-    "jg_ddpm_multiscale_loss": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
-                                c_f32, c_p],
-    "jg_gather_rows": [c_i32, c_p, c_i64, c_p, c_p, c_i32, c_i64, c_i32, c_i32, c_p],
-    "jg_scatter_rows": [c_i32, c_p, c_i64, c_p, c_p, c_i32, c_i64, c_i32, c_i32, c_p],
-    "jg_gather_rows_grouped": [c_i32, c_p, c_i64, c_p, c_p, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_scatter_rows_grouped": [c_i32, c_p, c_i64, c_p, c_p, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_l2norm_fwd": [c_p, c_p, c_p, c_i64, c_i32, c_f32, c_p],
-    "jg_l2norm_bwd": [c_p, c_p, c_p, c_p, c_i64, c_i32, c_f32, c_p],
-    "jg_lsgan_loss": [c_i32, c_p, c_f32, c_p, c_p, c_i64, c_i32, c_f32, c_f32, c_p],
-    "jg_gan_loss": [c_i32, c_i32, c_p, c_f32, c_p, c_p, c_i64, c_i32, c_f32, c_f32, c_p],
-    "jg_sgemm": [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i64, c_i64,
-                 c_i64, c_f32, c_f32, c_i32, c_i32, c_i32, c_p],
-    "jg_row_axpy": [c_p, c_p, c_p, c_i64, c_i32, c_p],
-    "jg_nce_sinkhorn_fwd": [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_nce_ce": [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i32, c_i32, c_f32, c_f32, c_p, c_p, c_f32, c_p],
-    "jg_nce_hdce": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_f32, c_f32, c_i32, c_i32, c_p],
-    "jg_nce_sinkhorn_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p],
-    "jg_layernorm_fwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_f32, c_p],
-    "jg_vit_attention_fwd": [c_i32, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_vit_attention_bwd": [c_i32, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_vit_tokens_fwd": [c_i32, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p],
-    "jg_vit_tokens_bwd": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_p],
-    "jg_gelu_fwd": [c_i32, c_p, c_p, c_i64, c_p],
-    "jg_gelu_bwd": [c_i32, c_p, c_p, c_p, c_i64, c_p],
-    "jg_layernorm_bwd_res": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p],
-    "jg_unpatchify": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_transpose2d": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_p],
-    "jg_layernorm_bwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p],
-    "jg_layernorm_bwd_add": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p],
-    "jg_layernorm_fwd_add": [c_i32, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_f32, c_p],
-    "jg_layernorm_bwd_add2": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i32, c_p],
-    "jg_dwconv3x3_fwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_dwconv3x3_bwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_dwconv3x3_bwd_ws": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_dwconv3x3_bwd_ws_floats": [c_i32, c_i32, c_i32, c_i32],
-    "jg_dwconv3x3_fwd_pad": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_dwconv3x3_bwd_ws_pad": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_attn_smallkv_fwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_f32, c_p],
-    "jg_attn_smallkv_bwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64,
-                            c_f32, c_p],
-    "jg_attn_smallkv_bwd2": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64,
-                             c_f32, c_p],
-    "jg_bilinear_fwd": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_p],
-    "jg_bilinear_bwd": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_p],
-    "jg_resize_sum_bwd_ws_floats": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32],
-    "jg_resize_sum_bwd": [c_i32, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p],
-    "jg_resize_sum": [c_i32, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p],
-    "jg_bilinear2_fwd": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_p],
-    "jg_bilinear2_bwd": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_p],
-    "jg_spectral_power_iter": [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_p],
-    "jg_spectral_weights": [c_i32, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_spectral_wgrad_fix": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p],
-    "jg_spectral_group_forward": [c_i32, c_p, c_i32, c_p, c_i64, c_p, c_i32, c_i32, c_i64, c_f32, c_p],
-    "jg_spectral_group_wgrad_fix": [c_p, c_i32, c_p, c_p, c_p, C.c_uint64, c_i64, c_p],
-    "jg_dwconv_affine_act_fwd": [c_i32, c_p, c_p, c_p, c_p, c_p] + [c_i32] * 11 + [c_p],
-    "jg_dwconv_affine_act_bwd": [c_i32, c_p, c_p, c_p, c_p, c_p] + [c_i32] * 11 + [c_p],
-    "jg_chan_affine_act_fwd": [c_i32, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_p],
-    "jg_chan_affine_act_bwd": [c_i32, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_p],
-    "jg_hinge_loss": [c_i32, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_f32, c_f32, c_p],
-    "jg_bn_coef": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_p],
-    "jg_bn_bwd_coef": [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_attn_compose_fwd": [c_i32, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_attn_compose_bwd": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_scale": [c_i32, c_p, c_p, c_p, c_p, c_i32, c_i64, c_i32, c_i32, c_p],
-    "jg_ddpm_p_sample": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_cm_noisy": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_cm_combine": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_cm_loss": [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32,
-                   c_f32, c_f32, c_f32, c_p],
-    "jg_cm_gan_head": [c_i32] + [c_p] * 13 + [c_i32] * 5 + [c_f32] * 3 + [c_p],
-    "jg_cm_gan_head_bwd": [c_i32] + [c_p] * 5 + [c_i32] * 5 + [c_p],
-    "jg_ect_loss": [c_i32] + [c_p] * 11 + [c_i64, c_p, c_p] + [c_i32] * 5 + [c_f32] * 3 + [c_p],
-    "jg_pixel_loss": [c_i32, c_p, c_p, c_p, c_i64, c_p] + [c_i32] * 8 + [c_f32, c_f32, c_p],
-    "jg_pixel_loss_bwd": [c_i32, c_p, c_p, c_p, c_p] + [c_i32] * 8 + [c_f32, c_f32, c_p],
-    "jg_d_aug": [c_i32, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f32, c_p, c_p, C.c_uint32, C.c_uint32] + [c_i32] * 5 + [c_p],
-    "jg_apa_update": [c_i32, c_p, c_i64, c_i64, c_p, c_p, c_p, c_f32, c_f32, c_f32, c_p],
-    "jg_d_diffusion": [c_i32, c_i32] + [c_p] * 8 + [c_i32, c_p, c_p, c_p, c_f32, c_p, C.c_uint32, c_p],
-    "jg_d_diffusion_bwd": [c_i32, c_i32] + [c_p] * 6 + [c_i32, c_p, c_p],
-    "jg_d_diffusion_update": [c_p] * 6 + [c_f32, c_f32, c_p, c_p, C.c_uint32, c_p],
-    "jg_d_diffusion_grid_cap": [],
-    "jg_cls_loss": [c_i32, c_i32, c_p, c_i64, c_p, c_i32, c_i32, c_f32, c_p, c_f32, c_p, c_p, c_i64, c_p, c_p, c_i32, c_p],
-    "jg_noise_level_embedding": [c_p, c_p, c_p, c_i32, c_i32, c_p],
-    "jg_noise_level_embedding_bwd": [c_p, c_p, c_p, c_p, c_i32, c_i32, c_p],
-    "jg_resample_u8": [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_resize_nearest_u8": [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_input_pipeline": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_lowres_roundtrip_f32": [c_p] * 14 + [c_i32] * 6 + [c_p],
-    "jg_lowres_roundtrip_band": [c_i32] * 5,
-    "jg_nhwc_to_nchw_f32": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_nchw_f32_to_nhwc": [c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p],
-    "jg_adamw_ema": [c_p, c_p, c_p, c_p, c_p, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_f32, c_f32, c_i32, c_p],
-    "jg_optim_step": [c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_f32, c_f32, c_i32, c_p, c_p, c_p],
-    "jg_adamw_ema_skip": [c_p, c_p, c_p, c_p, c_p, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_f32, c_f32, c_i32, c_p, c_p, c_p],
-    "jg_grad_nonfinite": [c_p, c_i64, c_p, c_p],
-    "jg_ema_update": [c_p, c_p, c_i64, c_f32, c_p],
-    "jg_refresh_weights": [c_i32, c_p, c_p, c_p, c_p, c_i32, c_p],
-}
+def parse_header(text: str):
+    """(constants, structs, signatures, restypes) of a header in the dialect of include/jg355.h: enums with explicit values,
+    `#define JG_X n`, typedef structs of scalars and pointers, prototypes `type jg_x(type name, ...);`.  Whatever else it finds raises."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts, structs, sigs, restypes = {}, {}, {}, {}
+    for name, val in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(JG_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M):
+        consts[name] = int(val)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    text = re.sub(r"typedef\s+void\s*\*\s*jg_stream_t\s*;", " ", text)
+
+    def enum(m):
+        for item in m.group(1).split(","):
+            im = re.fullmatch(r"\s*(JG_\w+)\s*=\s*(-?\d+)\s*", item)
+            if not im:
+                raise TypeError(f"jg355.h: enumerator `{item.strip()}` needs the form JG_X = n")
+            consts[im.group(1)] = int(im.group(2))
+        return " "
+
+    def struct(m):
+        fields = []
+        for decl in filter(str.strip, m.group(1).split(";")):
+            first, *more = decl.split(",")
+            ct = _ctype(first, structs, m.group(2))
+            if ct not in _SCALARS.values() and more:
+                raise TypeError(f"jg355.h: one pointer per declaration, `{decl.strip()}` in `{m.group(2)}`")
+            fields += [(re.findall(r"\w+", d)[-1], ct) for d in [first] + more]
+        structs[m.group(2)] = type(m.group(2), (C.Structure,), {"_fields_": fields})
+        return " "
+
+    def proto(m):
+        ret, name, params = m.group(1), m.group(2), m.group(3)
+        restypes[name] = _ctype(ret + " " + name, structs, name)
+        sigs[name] = [] if params.strip() == "void" else [_ctype(p, structs, name) for p in params.split(",")]
+        return " "
+
+    text = re.sub(r"enum\s*\{([^}]*)\}\s*;", enum, text)
+    text = re.sub(r"typedef\s+struct\s*\w*\s*\{([^}]*)\}\s*(\w+)\s*;", struct, text)
+    text = re.sub(r"([\w\s*]+?)\b(jg_\w+)\s*\(([^()]*)\)\s*;", proto, text)
+    if text.strip():
+        raise TypeError(f"jg355.h: not understood: `{' '.join(text.split())[:200]}`")
+    return consts, structs, sigs, restypes
+
+
+with open(HEADER) as _f:
+    CONSTANTS, STRUCTS, SIGNATURES, RESTYPES = parse_header(_f.read())      # name -> value / Structure class / argtypes / restype
+globals().update(CONSTANTS)         # JG_OK, JG_F16, JG_ACT_SILU, JG_OUT_STORE_T, JG_D_AUG_MAX, ...
+ConvArgs, WgradArgs = STRUCTS["jg_conv_args"], STRUCTS["jg_wgrad_args"]
 
 
 def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
@@ -225,7 +104,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     import time
     from concurrent.futures import ThreadPoolExecutor
 
-    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + [os.path.join(os.path.dirname(_HERE), "include", "jg355.h")]
+    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + [HEADER]
     hdr_time = max(os.path.getmtime(h) for h in hdrs)
     bdir = os.path.join(CSRC, "build")
     os.makedirs(bdir, exist_ok=True)
@@ -281,7 +160,7 @@ def lib():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(L, name)  # AttributeError if the symbol is absent
         fn.argtypes = argtypes
-        fn.restype = C.c_char_p if name in ("jg_strerror", "jg_last_kernel") else c_i64 if name.endswith("_ws_floats") else c_i32
+        fn.restype = RESTYPES[name]
     _lib = L
     return L
 

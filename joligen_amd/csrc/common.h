@@ -16,9 +16,16 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Dispatch switches: read ONCE from the environment, overridable at run time through the C ABI
 // (jg_set_tuning, include/jg355.h) so that tests can force a kernel configuration that the automatic choice would
 // not pick at test-sized shapes.  No per-launch getenv().
-enum JgTune { JG_TUNE_HALO_CFG = 0, JG_TUNE_WGRAD_HALO_CFG, JG_TUNE_CONV_VARIANT, JG_TUNE_WGRAD_VARIANT, JG_TUNE_SINKHORN_GENERIC,
-              JG_TUNE_CONV1X1, JG_TUNE_GN_REVERSE, JG_TUNE_HALO_DBG, JG_TUNE_PERSIST64, JG_TUNE_HALO_PIPE, JG_TUNE_WGRAD_PIPE, JG_TUNE_CONV_SPLITK, JG_TUNE_CONV_SMALL_TILE, JG_TUNE_GN_FUSED, JG_TUNE_GN_FUSED_CAP, JG_TUNE_GN_FUSED_DBG, JG_TUNE_GN_FUSED_SLEEP, JG_TUNE_WGRAD_LDS_PAD,
-              JG_TUNE_LN_BWD_CAP, JG_TUNE_DW_BWD_CAP, JG_TUNE_DW_BWD_PPT, JG_TUNE_CONV_KXK, JG_TUNE_CONV_RING, JG_TUNE_WGRAD_DEEP, JG_TUNE_WGRAD_SW, JG_TUNE_DETERMINISTIC, JG_TUNE_WGRAD_GROUP_BLOCKS, JG_TUNE_SGEMM_SPLIT, JG_TUNE_WGRAD_BIG, JG_TUNE_DW_RUN, JG_TUNE_COUNT };
+// The one list of the switches, X(name, default): JG_TUNE_<name> below and the environment variable "JG_<name>" (csrc/capi.hip).
+#define JG_TUNE_LIST(X) \
+  X(HALO_CFG, 0) X(WGRAD_HALO_CFG, 0) X(CONV_VARIANT, 6) X(WGRAD_VARIANT, 4) X(SINKHORN_GENERIC, 0) X(CONV1X1, 1) X(GN_REVERSE, 1) \
+  X(HALO_DBG, 0) X(PERSIST64, 1) X(HALO_PIPE, 1) X(WGRAD_PIPE, 1) X(CONV_SPLITK, 1) X(CONV_SMALL_TILE, 1) X(GN_FUSED, 1)           \
+  X(GN_FUSED_CAP, 256) X(GN_FUSED_DBG, 0) X(GN_FUSED_SLEEP, 4) X(WGRAD_LDS_PAD, 0) X(LN_BWD_CAP, 256) X(DW_BWD_CAP, 512)           \
+  X(DW_BWD_PPT, 8) X(CONV_KXK, 1) X(CONV_RING, 1) X(WGRAD_DEEP, 1) X(WGRAD_SW, 0) X(DETERMINISTIC, 0) X(WGRAD_GROUP_BLOCKS, 1024)  \
+  X(SGEMM_SPLIT, 0) X(WGRAD_BIG, 1) X(DW_RUN, 1)
+#define JG_TUNE_ENUM(name, dflt) JG_TUNE_##name,
+enum JgTune { JG_TUNE_LIST(JG_TUNE_ENUM) JG_TUNE_COUNT };
+#undef JG_TUNE_ENUM
 int jg_tune(int which);
 // dispatch sites record which kernel instance handled the launch (read back through jg_last_kernel(): bench.py / tools name the
 // roofline rows by what actually ran, not by a host-side guess of the dispatch)

@@ -916,7 +916,7 @@ __global__ __launch_bounds__(256) void cm_gan_head_bwd_kernel(const T* __restric
 // recomputes d and writes the gradient; block (0, 0) also writes the scalar.  No atomics: the same bits on every run.
 // grid = (blocks per sample, B); one pixel per thread and trip: one 16-byte load of each UNet output, the fp32 NCHW planes read along
 // the pixel index, one 16-byte store.
-constexpr int ECT_MAX_BLOCKS = 64;   // per sample; the workspace holds B * ECT_MAX_BLOCKS floats at most
+constexpr int ECT_MAX_BLOCKS = JG_ECT_MAX_BLOCKS;   // per sample; the workspace holds B * ECT_MAX_BLOCKS floats at most
 
 __device__ __forceinline__ void two_sum(float a, float b, float& s, float& e) {
 #pragma clang fp contract(off)
@@ -1025,7 +1025,7 @@ __global__ __launch_bounds__(256) void ect_grad_kernel(const T* __restrict__ Fn,
 // arrive with the pixel's load and are never selected.
 // Backward (pixel_grad_kernel): dx = g_s * lambda_s / N * (sign(d) | 2 d) with d recomputed and g_s read on the device, the product formed
 // in fp32 and rounded once; one 16-byte store per pixel, zeros in the pad channels and in an off segment.
-constexpr int PIXEL_MAX_BLOCKS = 256;   // per segment; the workspace holds S * PIXEL_MAX_BLOCKS floats at most
+constexpr int PIXEL_MAX_BLOCKS = JG_PIXEL_MAX_BLOCKS;   // per segment; the workspace holds S * PIXEL_MAX_BLOCKS floats at most
 
 template <typename T>
 __global__ __launch_bounds__(256) void pixel_partial_kernel(const T* __restrict__ x, const T* __restrict__ y, float* __restrict__ partial,

@@ -16,7 +16,7 @@
 
 namespace {
 constexpr int LR_THREADS = 1024;
-constexpr int LR_MAX_TAPS = 65;        // down-pass taps per output position (ratio <= 32)
+constexpr int LR_MAX_TAPS = JG_LOWRES_MAX_TAPS;        // down-pass taps per output position (ratio <= 32)
 constexpr int LR_UP_TAPS = 3;          // an up pass has support 1: K = 3
 constexpr int LR_MAX_BAND = 64;
 constexpr int LR_LDS_BIG = 40000;      // floats: 156 KiB of the 160 KiB, one workgroup (16 waves) per CU

@@ -712,8 +712,8 @@ class Diffusion(nn.Module):
 
     def __init__(self, t_min=5, t_max=500, noise_std=0.5):
         super().__init__()
-        if (t_min, t_max) != (5, 500):
-            raise NotImplementedError("the update kernel is built for t_min = 5, t_max = 500 (projector.py:533-535)")
+        if (t_min, t_max) != (_lib.JG_D_DIFFUSION_T_MIN, _lib.JG_D_DIFFUSION_T_MAX):
+            raise NotImplementedError("the update kernel is built for the reference's t_min = 5, t_max = 500 (projector.py:533-535)")
         self.t_min, self.t_max, self.noise_std = t_min, t_max, float(noise_std)
         st = ops.DDiffusionState.fresh("cpu")
         for name, t in zip(("p", "Tn", "alphas_bar_sqrt", "one_minus_alphas_bar_sqrt", "t_epl"), st.tensors()):

@@ -1773,7 +1773,7 @@ def cm_gan_head(F_next, F_cur, noisy_next, noisy_cur, cs_n, co_n, cs_c, co_c, ma
 
 
 ECT_C = 1e-6                 # CMModel.c (cm_model.py:120)
-_ECT_MAX_BLOCKS = 64         # per-sample partial sums of jg_ect_loss (csrc/elementwise.hip)
+_ECT_MAX_BLOCKS = _lib.JG_ECT_MAX_BLOCKS         # per-sample partial sums of jg_ect_loss (csrc/elementwise.hip)
 
 
 def _ect_loss_launch(Fn, Fc, noisy_n, noisy_c, cs_n, co_n, cs_c, co_c, mask, dt, lam, grad_scale):
@@ -1831,7 +1831,7 @@ def ect_loss(F_next, F_cur, noisy_next, noisy_cur, cs_n, co_n, cs_c, co_c, mask,
 
 
 PIXEL_OFF, PIXEL_L1, PIXEL_MSE = 0, 1, 2       # segment modes of jg_pixel_loss
-_PIXEL_MAX_BLOCKS = 256                        # per-segment partial sums of jg_pixel_loss (csrc/elementwise.hip)
+_PIXEL_MAX_BLOCKS = _lib.JG_PIXEL_MAX_BLOCKS   # per-segment partial sums of jg_pixel_loss (csrc/elementwise.hip)
 
 
 def _pixel_loss_check(x, y, C, modes, lambdas):
@@ -1902,7 +1902,7 @@ def pixel_loss(x, y, C, modes, lambdas):
 
 # ---- class loss of the semantic-consistency branch (train_semantic_cls; csrc/sem_cls.hip) -------------------------------------------------
 CLS_CE, CLS_MSE, CLS_L1 = 0, 1, 2              # modes of jg_cls_loss
-_CLS_DT = {torch.float16: _lib.JG_F16, torch.bfloat16: _lib.JG_BF16, torch.float32: 2}      # 2: JG_CLS_F32 of include/jg355.h
+_CLS_DT = {torch.float16: _lib.JG_F16, torch.bfloat16: _lib.JG_BF16, torch.float32: _lib.JG_CLS_F32}
 
 
 def _cls_loss_check(logits, target, mode, prev, state):
@@ -1978,7 +1978,7 @@ def cls_loss(logits, target, mode=CLS_CE, lam=1.0, prev=None, threshold=1.0, sta
 
 
 # ---- discriminator-input augmentations: dataaug_D_noise and adaptive pseudo augmentation (csrc/d_aug.hip) ----------------------------------
-D_AUG_MAX = 4                  # targets of one jg_d_aug launch (JG_D_AUG_MAX of include/jg355.h)
+D_AUG_MAX = _lib.JG_D_AUG_MAX  # targets of one jg_d_aug launch
 D_AUG_NOISE_STREAM = 0         # Philox stream id of the noise; the flags of target d draw on stream 1 + d unless the caller says otherwise
 
 
@@ -2074,7 +2074,7 @@ def apa_update(pred, state, target, num, den, channel0=False):
 
 
 # ---- dataaug_D_diffusion: Diffusion-GAN noise on the projected discriminator's backbone features (csrc/d_diffusion.hip) ---------------------
-D_DIFFUSION_MAX, D_DIFFUSION_TABLE, D_DIFFUSION_EPL = 4, 501, 64      # JG_D_DIFFUSION_* of include/jg355.h
+D_DIFFUSION_MAX, D_DIFFUSION_TABLE, D_DIFFUSION_EPL = _lib.JG_D_DIFFUSION_MAX, _lib.JG_D_DIFFUSION_TABLE, _lib.JG_D_DIFFUSION_EPL
 
 
 class DDiffusionState:
@@ -2088,7 +2088,7 @@ class DDiffusionState:
 
     @classmethod
     def fresh(cls, device):
-        st = cls(torch.zeros(1, device=device), torch.tensor([5, 0], device=device, dtype=torch.int32),
+        st = cls(torch.zeros(1, device=device), torch.tensor([_lib.JG_D_DIFFUSION_T_MIN, 0], device=device, dtype=torch.int32),
                  torch.zeros(D_DIFFUSION_TABLE, device=device), torch.zeros(D_DIFFUSION_TABLE, device=device),
                  torch.zeros(D_DIFFUSION_EPL, device=device, dtype=torch.int32))
         st.a[0] = 1.0

@@ -11,10 +11,9 @@ import torch
 
 from ._autograd import JGFunction
 from . import _lib
-from ._lib import check
+from ._lib import JG_ACT_NONE, JG_ACT_RELU, check
 from .ops import _DT, _dt, _p, _require_cuda, _st, copy_channels
 
-JG_ACT_NONE, JG_ACT_RELU = 0, 2
 # depth-wise 3x3 weight gradient: per-block partials through a workspace + one summing launch (1) or atomics from every block (0)
 DW_TWO_PHASE = os.environ.get("JG_DW_TWO_PHASE", "1") != "0"
 # round 6: backward of resize_sum through jg_resize_sum_bwd (separable adjoint, two launches); 0 = activation gradient + one gather launch per term

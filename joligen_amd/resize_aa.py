@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 
-MAX_TAPS = 65      # JG_LOWRES_MAX_TAPS of csrc/resize_aa.hip: taps per output position the kernel accepts for the down pass
+MAX_TAPS = _lib.JG_LOWRES_MAX_TAPS      # taps per output position the kernel accepts for the down pass
 
 
 def aa_bilinear_tables(n_in, n_out):

@@ -13,55 +13,167 @@ import jg_oracle as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_c_abi_exports_every_declared_symbol():
+def _header():
+    """include/jg355.h without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "jg355.h")).read(), flags=re.S)
+
+
+def _declared(hdr):
+    """what the header declares, found WITHOUT the parser of joligen_amd._lib: function names, {struct: field names}, constant names"""
+    funcs = sorted(set(re.findall(r"\b(jg_[a-z0-9_]+)\s*\(", hdr)) - {"jg_stream_t"})
+    structs = {name: re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*[;,]", body)
+               for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", hdr, flags=re.S)}
+    return funcs, structs, sorted(set(re.findall(r"\bJG_[A-Z0-9_]+\b", hdr)))
+
+
+@pytest.fixture(scope="module")
+def compiler_view(tmp_path_factory):
+    """What g++ makes of include/jg355.h: per function the result code + one code per parameter (from decltype(&jg_x): nothing is
+    linked), sizeof and every field offset of every struct, the value of every JG_* constant."""
+    funcs, structs, consts = _declared(_header())
+    lines = ['#include <cstdio>\n#include <cstddef>\n#include "jg355.h"\n'
+             'template <class T> struct code { static_assert(sizeof(T) == 0, "type outside the ABI"); };\n'
+             "template <class T> struct code<T*> { static constexpr char v = 'p'; };\n"]
+    lines += [f"template <> struct code<{t}> {{ static constexpr char v = '{c}'; }};\n"
+              for t, c in (("const char*", "s"), ("int32_t", "i"), ("int64_t", "l"), ("uint32_t", "u"), ("uint64_t", "U"), ("float", "f"))]
+    lines += ['template <class R, class... A> void sig(const char* name, R (*)(A...)) {\n  printf("F %s %c ", name, code<R>::v);\n'
+              '  (putchar(code<A>::v), ...);\n  putchar(\'\\n\');\n}\nint main() {\n']
+    lines += [f'  sig("{n}", (decltype(&{n}))nullptr);\n' for n in funcs]
+    for st, fields in structs.items():
+        lines.append(f'  printf("S {st} %zu\\n", sizeof({st}));\n')
+        lines += [f'  printf("O {st}.{f} %zu\\n", offsetof({st}, {f}));\n' for f in fields]
+    lines += [f'  printf("C {c} %lld\\n", (long long){c});\n' for c in consts]
+    d = tmp_path_factory.mktemp("abi")
+    (d / "abi.cpp").write_text("".join(lines) + "  return 0;\n}\n")
+    subprocess.run(["g++", "-std=c++17", "-I", os.path.join(ROOT, "include"), str(d / "abi.cpp"), "-o", str(d / "abi")], check=True)
+    view = {"F": {}, "S": {}, "O": {}, "C": {}}
+    for kind, name, *rest in (ln.split() for ln in subprocess.run([str(d / "abi")], check=True, capture_output=True, text=True).stdout.splitlines()):
+        view[kind][name] = (rest[0], rest[1] if len(rest) > 1 else "") if kind == "F" else int(rest[0])
+    return view
+
+
+def test_c_abi_exports_every_declared_symbol(compiler_view):
+    """every declared entry point is bound with the argument and result types the compiler sees, and the library exports it"""
+    import ctypes as C
+
     from joligen_amd import _lib
 
     path = _lib.build()
-    header = open(os.path.join(ROOT, "include", "jg355.h")).read()
-    declared = set(re.findall(r"\b(jg_[a-z0-9_]+)\s*\(", header))
-    declared -= {"jg_stream_t"}
-    assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    declared = set(_declared(_header())[0])
+    assert declared == set(_lib.SIGNATURES) == set(_lib.RESTYPES) == set(compiler_view["F"]), declared ^ set(_lib.SIGNATURES)
+    codes = {C.c_int32: "i", C.c_int64: "l", C.c_uint32: "u", C.c_uint64: "U", C.c_float: "f", C.c_char_p: "s", C.c_void_p: "p"}
+
+    def code(t):
+        return "p" if issubclass(t, C._Pointer) else codes[t]
+
+    mine = {n: (code(_lib.RESTYPES[n]), "".join(code(t) for t in _lib.SIGNATURES[n])) for n in _lib.SIGNATURES}
+    assert mine == compiler_view["F"], {n: (mine[n], compiler_view["F"][n]) for n in mine if mine[n] != compiler_view["F"][n]}
+    assert _lib.SIGNATURES["jg_conv2d_nt"][1] is C.POINTER(_lib.ConvArgs) and _lib.SIGNATURES["jg_conv2d_wgrad_tn"][1] is C.POINTER(_lib.WgradArgs)
     nm = subprocess.run(["nm", "-D", path], check=True, capture_output=True, text=True).stdout
     for name in declared:
         assert f" T {name}" in nm, name
     L = _lib.lib()  # dlopen + argtypes; no compute call (no GPU here)
+    assert all(getattr(L, n).argtypes == _lib.SIGNATURES[n] and getattr(L, n).restype is _lib.RESTYPES[n] for n in declared)
     assert L.jg_version() >= 100
     assert b"bad argument" in L.jg_strerror(-1)
 
 
-def test_struct_layout_matches_header(tmp_path):
-    """ctypes mirrors of jg_conv_args / jg_wgrad_args: field order as in the header, and sizes / offsets equal
-    to what a C compiler makes of include/jg355.h (gcc)."""
+def test_struct_layout_matches_header(compiler_view):
+    """ctypes mirrors of jg_conv_args / jg_wgrad_args (and every other struct of the header): field order as in the header, and the size
+    and the offset of EVERY field equal to what a C++ compiler makes of include/jg355.h (g++)."""
     import ctypes as C
-    import subprocess
 
-    from joligen_amd._lib import ConvArgs, WgradArgs
+    from joligen_amd import _lib
 
-    hdr = open(os.path.join(ROOT, "include", "jg355.h")).read()
-    nocomment = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    body = nocomment[nocomment.index("typedef struct {"):nocomment.index("} jg_conv_args;")]
-    names = re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*[;,]", body)
-    assert names == [f[0] for f in ConvArgs._fields_], names
-    body = nocomment[nocomment.index("} jg_conv_args;"):]
-    body = body[body.index("typedef struct {"):body.index("} jg_wgrad_args;")]
-    names = re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*[;,]", body)
-    assert names == [f[0] for f in WgradArgs._fields_], names
-    # the compiler's view of the two structs
-    probe = ["stats", "ldstats", "gn_x", "gn_act", "ldx", "sxb", "alpha"]
-    wprobe = ["lddy", "sdyb", "alpha", "dbias_scale"]
-    src = tmp_path / "layout.c"
-    src.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "jg355.h"\nint main(void) {\n'
-        '  printf("%zu %zu", sizeof(jg_conv_args), sizeof(jg_wgrad_args));\n'
-        + "".join(f'  printf(" %zu", offsetof(jg_conv_args, {n}));\n' for n in probe)
-        + "".join(f'  printf(" %zu", offsetof(jg_wgrad_args, {n}));\n' for n in wprobe)
-        + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    vals = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    mine = [C.sizeof(ConvArgs), C.sizeof(WgradArgs)] + [getattr(ConvArgs, n).offset for n in probe] \
-        + [getattr(WgradArgs, n).offset for n in wprobe]
-    assert vals == mine, (vals, mine)
+    structs = _declared(_header())[1]
+    assert set(structs) == set(_lib.STRUCTS) == set(compiler_view["S"]) and {"jg_conv_args", "jg_wgrad_args"} <= set(structs)
+    assert _lib.ConvArgs is _lib.STRUCTS["jg_conv_args"] and _lib.WgradArgs is _lib.STRUCTS["jg_wgrad_args"]
+    assert (len(structs["jg_conv_args"]), len(structs["jg_wgrad_args"])) == (47, 34)
+    for st, names in structs.items():
+        cls = _lib.STRUCTS[st]
+        assert names == [f[0] for f in cls._fields_], (st, names)
+        assert C.sizeof(cls) == compiler_view["S"][st], st
+        mine = {f"{st}.{n}": getattr(cls, n).offset for n in names}
+        theirs = {k: v for k, v in compiler_view["O"].items() if k.startswith(st + ".")}
+        assert mine == theirs, (st, mine, theirs)
+
+
+def test_constants_come_from_the_header(compiler_view):
+    """every JG_* enum / #define value as the compiler sees it, and the Python names that size a workspace or refuse a shape by them"""
+    from joligen_amd import _lib, ops, resize_aa
+
+    assert _lib.CONSTANTS == compiler_view["C"]
+    assert all(getattr(_lib, n) == v for n, v in compiler_view["C"].items())
+    c = compiler_view["C"]
+    assert ops._ECT_MAX_BLOCKS == c["JG_ECT_MAX_BLOCKS"] == 64 and ops._PIXEL_MAX_BLOCKS == c["JG_PIXEL_MAX_BLOCKS"] == 256
+    assert resize_aa.MAX_TAPS == c["JG_LOWRES_MAX_TAPS"] == 65
+    assert ops._CLS_DT[torch.float32] == c["JG_CLS_F32"] == 2 and ops._CLS_DT[torch.float16] == c["JG_F16"] and ops._CLS_DT[torch.bfloat16] == c["JG_BF16"]
+    assert ops.D_AUG_MAX == c["JG_D_AUG_MAX"] == 4
+    assert (ops.D_DIFFUSION_MAX, ops.D_DIFFUSION_TABLE, ops.D_DIFFUSION_EPL) == (c["JG_D_DIFFUSION_MAX"], c["JG_D_DIFFUSION_TABLE"], c["JG_D_DIFFUSION_EPL"]) == (4, 501, 64)
+
+
+def test_header_parser_refuses_unknown_types():
+    """the type map is closed: a declaration outside it is an error that names the declaration, never a void* guess"""
+    from joligen_amd import _lib
+
+    consts, structs, sigs, res = _lib.parse_header("enum { JG_A = 3 };\ntypedef struct { const float* p; int32_t a, b; } jg_t;\n"
+                                                   "int64_t jg_x(int n, const jg_t* t, const char* s, float* const* q);")
+    assert consts == {"JG_A": 3} and [f[0] for f in structs["jg_t"]._fields_] == ["p", "a", "b"]
+    assert sigs == {"jg_x": [_lib.c_i32, _lib.C.POINTER(structs["jg_t"]), _lib.C.c_char_p, _lib.c_p]} and res == {"jg_x": _lib.c_i64}
+    with pytest.raises(TypeError, match="jg_x"):
+        _lib.parse_header("int jg_x(int n, double v);")
+    with pytest.raises(TypeError, match="jg_t"):
+        _lib.parse_header("typedef struct { int32_t n; double v; } jg_t;")
+    for text in ("int jg_x(unsigned n);", "int jg_x(jg_t by_value);", "typedef struct { int32_t n[4]; } jg_t;", "enum { JG_A, JG_B };",
+                 "static int jg_count;", "int jg_x(int (*callback)(int));"):
+        with pytest.raises(TypeError):
+            _lib.parse_header(text)
+
+
+# (name, default) of every dispatch switch, as the table of csrc/capi.hip stood before it was generated from JG_TUNE_LIST
+_TUNE_DEFAULTS = [("HALO_CFG", 0), ("WGRAD_HALO_CFG", 0), ("CONV_VARIANT", 6), ("WGRAD_VARIANT", 4), ("SINKHORN_GENERIC", 0), ("CONV1X1", 1),
+                  ("GN_REVERSE", 1), ("HALO_DBG", 0), ("PERSIST64", 1), ("HALO_PIPE", 1), ("WGRAD_PIPE", 1), ("CONV_SPLITK", 1),
+                  ("CONV_SMALL_TILE", 1), ("GN_FUSED", 1), ("GN_FUSED_CAP", 256), ("GN_FUSED_DBG", 0), ("GN_FUSED_SLEEP", 4),
+                  ("WGRAD_LDS_PAD", 0), ("LN_BWD_CAP", 256), ("DW_BWD_CAP", 512), ("DW_BWD_PPT", 8), ("CONV_KXK", 1), ("CONV_RING", 1),
+                  ("WGRAD_DEEP", 1), ("WGRAD_SW", 0), ("DETERMINISTIC", 0), ("WGRAD_GROUP_BLOCKS", 1024), ("SGEMM_SPLIT", 0),
+                  ("WGRAD_BIG", 1), ("DW_RUN", 1)]
+
+_TUNE_CHILD = """
+import json, sys
+from joligen_amd import _lib
+L = _lib.lib()
+names = json.loads(sys.argv[1])
+out = {"defaults": [L.jg_get_tuning(n.encode()) for n in names], "get_unknown": L.jg_get_tuning(b"JG_NO_SUCH_SWITCH"),
+       "set_unknown": L.jg_set_tuning(b"JG_NO_SUCH_SWITCH", 1), "prev": [], "back": []}
+for n in names:
+    v = L.jg_get_tuning(n.encode()) + 7
+    out["prev"].append(_lib.set_tuning(n, v))
+    out["back"].append(L.jg_get_tuning(n.encode()) - v)
+out["after"] = [L.jg_get_tuning(n.encode()) for n in names]
+out["torch"] = "torch" in sys.modules
+print(json.dumps(out))
+"""
+
+
+def test_dispatch_switch_table_defaults_and_round_trip():
+    """names, defaults and the set / get round trip of the 30 dispatch switches, in a fresh process without any JG_* variable in its
+    environment (no GPU is initialised: the child never imports torch and launches nothing)"""
+    import json
+    import sys
+
+    from joligen_amd import _lib
+
+    _lib.build()
+    assert len(_TUNE_DEFAULTS) == 30
+    names = ["JG_" + n for n, _ in _TUNE_DEFAULTS]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("JG_")}
+    r = subprocess.run([sys.executable, "-c", _TUNE_CHILD, json.dumps(names)], cwd=ROOT, env=env, check=True, capture_output=True, text=True)
+    out = json.loads(r.stdout.splitlines()[-1])
+    assert dict(zip(names, out["defaults"])) == {"JG_" + n: d for n, d in _TUNE_DEFAULTS}
+    assert out["get_unknown"] == -1 and out["set_unknown"] == _lib.JG_ERR_BAD_ARG
+    assert out["prev"] == out["defaults"] and out["back"] == [0] * 30       # every name sets its own slot ...
+    assert out["after"] == [d + 7 for _, d in _TUNE_DEFAULTS]                # ... and no other name's
+    assert out["torch"] is False
 
 
 @pytest.mark.parametrize("name", ["tiny_eff", "tiny_noeff", "tiny_attn"])
