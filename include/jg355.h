@@ -49,6 +49,9 @@ const char* jg_last_kernel(void);
  * with A the implicit im2col of x[z] = [B,H,W,Cin] (pixel stride ldx), m = (b,oh,ow),
  * k = (r,s,ci), zero padding `pad`, stride `stride`.  R=S=1,pad=0 gives a plain GEMM.
  * z = zb*nh + zh with element strides (s*b, s*h) per operand.  out_f32: y is fp32 else T.
+ * x, y and res may each be a channel slice of a wider buffer on its own stride: the kernel chosen and the values
+ * stored do not depend on ldx / ldy / ldres, except that the streaming kernel of the 8-channel stem (Cin 8, 3x3, >= 65536 pixels)
+ * serves ldx == 8 only and an x slice of that shape runs on the generic kernel.
  * Replaces nn.Conv2d / nn.Conv1d(k=1) forward and -- with the flipped/transposed weight
  * copy of jg_refresh_weights -- its input-gradient
  * (models/modules/unet_generator_attn/unet_generator_attn.py:186-220,297,305,482,635-642),

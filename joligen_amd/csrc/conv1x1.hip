@@ -308,6 +308,7 @@ void launch_c8(const ConvP& p, hipStream_t st) {
   int bx = (ntiles + 3) / 4;
   const int cap = 256 * 8 / ngroups > 64 ? 256 * 8 / ngroups : 64;
   if (bx > cap) bx = cap;
+  jg_note_kernel("conv3x3_c8_stream_kernel");
   hipLaunchKernelGGL((conv3x3_c8_stream_kernel<T, 2>), dim3(bx, ngroups), dim3(256), 0, st, p, ntiles);
 }
 

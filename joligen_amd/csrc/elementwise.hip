@@ -53,7 +53,7 @@ __global__ void upsample2x_kernel(const T* __restrict__ x, long ldx, T* __restri
       for (int q = 0; q < 8; ++q) f[q] *= scale;
       v = pack8<T>(f);
     }
-    *reinterpret_cast<uint4*>(y + i * 8) = v;
+    *reinterpret_cast<uint4*>(y + (i / noct) * ldy + co * 8) = v;      // i / noct = the output pixel; y carries its own pixel stride
   }
 }
 

@@ -580,11 +580,16 @@ int launch_conv(const ConvP& p, int nbatch, hipStream_t st, long ws_bytes) {
       jg_note_kernel("conv_nt_glds_kernel<256,32,64,4,1>");      // <= 32 output channels (7x7 content / output heads): no half-empty 64-wide tile
       launch_glds<T, 256, 32, 64, 4, 1>(p, nbatch, st, ws_bytes);
     } else if (p.N <= 64) {
-      if (variant == 3 || variant >= 6) launch_glds<T, 256, 64, 64, 4, 1>(p, nbatch, st, ws_bytes);
-      else launch_glds<T, 256, 64, 32, 4, 1>(p, nbatch, st);
+      if (variant == 3 || variant >= 6) {
+        jg_note_kernel("conv_nt_glds_kernel<256,64,64,4,1>");      // (launch_glds renames it when it cuts the K loop)
+        launch_glds<T, 256, 64, 64, 4, 1>(p, nbatch, st, ws_bytes);
+      } else launch_glds<T, 256, 64, 32, 4, 1>(p, nbatch, st);
     } else {
       if (variant == 2) launch_glds<T, 128, 128, 32, 2, 2>(p, nbatch, st);
-      else if (variant == 3 || variant >= 6) launch_glds<T, 128, 128, 64, 2, 2>(p, nbatch, st, ws_bytes);
+      else if (variant == 3 || variant >= 6) {
+        jg_note_kernel("conv_nt_glds_kernel<128,128,64,2,2>");
+        launch_glds<T, 128, 128, 64, 2, 2>(p, nbatch, st, ws_bytes);
+      }
       else if (variant == 4) launch_glds<T, 256, 128, 32, 2, 2>(p, nbatch, st);
       else launch_glds<T, 256, 128, 64, 2, 2>(p, nbatch, st);
     }

@@ -1024,10 +1024,12 @@ extern "C" int jg_conv2d_wgrad_tn(int dtype, const jg_wgrad_args* a, jg_stream_t
     JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((wgrad_tn_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, p););
   } else if (p.Cout <= 64 && variant != 3) {
     dim3 grid(tilesN, 1, a->nbatch * p.splitk);
+    jg_note_kernel("wgrad_tn_tr_kernel<1>");
     if (jg_tune(JG_TUNE_WGRAD_DEEP) & 1) { JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((wgrad_tn_tr_kernel<T, 1, true>), grid, dim3(256), 0, (hipStream_t)stream, p);); }
     else { JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((wgrad_tn_tr_kernel<T, 1>), grid, dim3(256), 0, (hipStream_t)stream, p);); }
   } else {
     dim3 grid(((p.Cout + 127) / 128) * tilesN, 1, a->nbatch * p.splitk);
+    jg_note_kernel("wgrad_tn_tr_kernel<2>");
     if (jg_tune(JG_TUNE_WGRAD_DEEP) & 2) { JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((wgrad_tn_tr_kernel<T, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, p);); }
     else { JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((wgrad_tn_tr_kernel<T, 2>), grid, dim3(256), 0, (hipStream_t)stream, p);); }
   }
