@@ -128,6 +128,26 @@ def relerr(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
+def row_errors(got, ref):
+    """per-row error ||got_r - ref_r||_2 / (||ref||_F / sqrt(nrows)), a row being the last-dimension vector: relative to the RMS row norm of the
+    reference, so that a row whose true value is tiny does not blow up.  Independent roundings give every row the norm-wise relative error."""
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    assert got.shape == ref.shape, (tuple(got.shape), tuple(ref.shape))
+    got, ref = got.reshape(-1, got.shape[-1]), ref.reshape(-1, ref.shape[-1])
+    rms = float(ref.norm()) / (ref.shape[0] ** 0.5) + 1e-30
+    return (got - ref).norm(dim=1) / rms
+
+
+def assert_rows_close(got, ref, bound, what, worst=5):
+    """every row of `got` within `bound` of `ref` (row_errors); reports the worst few (row index, error) pairs"""
+    e = row_errors(got, ref)
+    assert not bool(torch.isnan(e).any()), f"{what}: NaN in rows {torch.isnan(e).nonzero()[:worst, 0].tolist()}"
+    top = torch.topk(e, min(worst, e.numel()))
+    pairs = [(int(i), float(f"{float(v):.3e}")) for v, i in zip(top.values, top.indices)]
+    assert float(top.values[0]) < bound, f"{what}: {int((e >= bound).sum())} of {e.numel()} rows outside the per-row bound {bound:.1e}; worst (row, error): {pairs}"
+    return pairs[0]
+
+
 def _default_last_kernel():
     from joligen_amd import _lib
 
@@ -145,22 +165,25 @@ def _default_sync():
         torch.cuda.synchronize()
 
 
-def run_pair(launch, operands, *, kind=EXEC_LIKE, tuning=None, device="cpu", guard=3, fixed=(), last_kernel=_default_last_kernel,
+def run_pair(launch, operands, *, kind=EXEC_LIKE, tuning=None, device="cpu", guard=3, fixed=(), share=None, last_kernel=_default_last_kernel,
              set_tuning=_default_set_tuning, sync=_default_sync):
     """Run `launch(views)` twice under the same tuning switches: on contiguous operands (left = right = 0, guards kept), then on slices that hold
-    the same values, every operand on its own stride (`placement(kind, i)`; names in `fixed` stay contiguous).
+    the same values, every operand on its own stride (`placement(kind, i)`; names in `fixed` stay contiguous; `share` = {name: other} places
+    `name` as `other` is placed, for entry points that take ONE stride for two operands, such as q and dq of jg_attn_smallkv_bwd2).
     operands: {name: Operand}; launch receives {name: view} and reads pixel strides from view.stride(-2).
     Returns Pair(contig views, strided views, contig buffers, strided buffers, (kernel after run 1, kernel after run 2), launch's returns)."""
     prev = {k: set_tuning(k, v) for k, v in (tuning or {}).items()}
+    share = share or {}
+    index = {name: i for i, name in enumerate(operands)}
     try:
         runs = []
         for strided in (False, True):
             bufs, views = {}, {}
             for i, (name, op) in enumerate(operands.items()):
-                left, right = placement(kind, i, op.unit) if strided and name not in fixed else (0, 0)
+                left, right = placement(kind, index[share.get(name, name)], op.unit) if strided and name not in fixed else (0, 0)
                 bufs[name], views[name] = make_slice(op.shape, op.dtype, op.seed, left=left, right=right, guard=guard, role=op.role,
                                                      values=op.values, scale=op.scale, device=device)
-            pads = [b.spec.ld - b.spec.shape[3] for n, b in bufs.items() if strided and n not in fixed]
+            pads = [b.spec.ld - b.spec.shape[3] for n, b in bufs.items() if strided and n not in fixed and n not in share]
             assert len(set(pads)) == len(pads), pads
             ret = launch(views)
             sync()

@@ -105,3 +105,35 @@ def test_statistics_rows_and_accumulators():
     su.flat_of(view)[0][0] = 0.0
     with pytest.raises(AssertionError, match=r"\(-2, -16\)"):
         su.assert_canary_intact(buf)
+
+
+def test_rows_close_flags_one_bad_row_that_the_norm_hides():
+    """one wrong token row of a [2, 257, 384] bf16 output (20 % off) stays under the norm-wise bf16 bound of test_gpu_8_projd_vit.py (TOL = 1.2e-2:
+    diluted by sqrt(514 rows)) and is caught by the per-row bound at 4 x that TOL"""
+    tol = 1.2e-2
+    ref = torch.randn(2, 257, 384, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+    got = ref.to(torch.bfloat16)
+    assert su.relerr(got, ref) < tol and su.assert_rows_close(got, ref, 4 * tol, "clean")[1] < tol
+    got[1, 256] = (1.2 * ref[1, 256]).to(torch.bfloat16)         # the last (clamped tail) row of the last image
+    assert su.relerr(got, ref) < tol, su.relerr(got, ref)
+    e = su.row_errors(got, ref)
+    assert e.shape == (514,) and int(e.argmax()) == 513 and 0.15 < float(e[513]) < 0.25
+    with pytest.raises(AssertionError, match=r"1 of 514 rows outside the per-row bound.*\(513, "):
+        su.assert_rows_close(got, ref, 4 * tol, "o")
+    # relative to the RMS row norm: a row whose true value is tiny does not blow up
+    ref[0, 3] *= 1e-6
+    small = ref.to(torch.bfloat16)
+    assert float(su.row_errors(small, ref)[3]) < 1e-6
+    small[0, 5, 0] = float("nan")
+    with pytest.raises(AssertionError, match=r"NaN in rows \[5\]"):
+        su.assert_rows_close(small, ref, 4 * tol, "o")
+
+
+def test_shared_placement():
+    """share = {name: other}: both operands on ONE stride in the strided launch, every other operand still on its own"""
+    ops = {"x": su.Operand((B, H, W, C), torch.float16, "in", 1), "y": su.Operand((B, H, W, C), torch.float16, "out"),
+           "res": su.Operand((B, H, W, C), torch.float16, "in", 2)}
+    pair = su.run_pair(standin, ops, kind=su.ABI_MIN, share={"res": "x"}, last_kernel=lambda: "standin", set_tuning=lambda k, v: 0, sync=lambda: None)
+    su.verify(pair, exact=["y"], kernel="standin")
+    assert pair.strided["res"].stride(-2) == pair.strided["x"].stride(-2) != pair.strided["y"].stride(-2)
+    assert pair.contig["res"].stride(-2) == C
