@@ -102,7 +102,12 @@ typedef struct {
   int32_t x_mode;
   /* y_mode 1: y is [B, Ho/2, Wo/2, Cout] and receives the 2x2 SUM-pool of alpha * conv(x) -- the adjoint of x_mode 1, i.e. the
    * input gradient of `conv(Upsample(h))` w.r.t. h, without the full-resolution gradient in between.  No bias / res / stats;
-   * halo-resident 3x3 kernel only, else JG_ERR_UNSUPPORTED. */
+   * halo-resident 3x3 kernel only, else JG_ERR_UNSUPPORTED.
+   * y_mode 2: the same result in its sub-pixel (gather) form: w is the TRANSPOSED folded weight tensor [4][Cout][2][2][Cin] of
+   * jg_subpixel_fold_pair (its `outT`; ldw = 4 * Cin; Cin / Cout in the sense of THIS call: Cin = channels of x = dO, Cout = channels of
+   * the result), R = S = 3, pad 1 in the args.  Every low-resolution pixel sums the four parity sub-images of x through 2x2 taps: 16
+   * instead of 36 tap-MACs per result pixel.  Same restrictions as y_mode 1, the shape limits of x_mode 2 (H, W multiples of 32, Cin and
+   * Cout multiples of 64) and B * H * W * ldx < 2^31; JG_ERR_UNSUPPORTED outside them. */
   int32_t y_mode;
   /* optional fp32 scratch for the split-K form of the generic kernel (16-byte aligned, ws_bytes long, contents irrelevant on entry and
    * on return).  Layers with few output tiles and a long reduction -- the discriminators' 4x4 stride-2 convolutions at 16x16 .. 4x4
@@ -132,6 +137,10 @@ int jg_conv1x1_gn_bwd_apply(int dtype, const jg_conv_args* a, const void* gn_x, 
  * 3x3 taps that land on tap (a, b) of output phase (py, px) of conv3x3(Upsample_nearest(x)) -- per axis {w0 | w1+w2} for phase 0,
  * {w0+w1 | w2} for phase 1 (fp32 sum, one rounding). */
 int jg_subpixel_fold(int dtype, const float* w32, void* out, int Cout, int Cin, jg_stream_t s);
+/* The folded weights of a layer for both directions in ONE launch: `out` exactly as jg_subpixel_fold writes it (bit-identical), and
+ * outT[py*2+px][ci][a][b][co] (dtype) = out[py*2+px][co][a][b][ci], the weight tensor of jg_conv_args.y_mode 2 (the sub-pixel input
+ * gradient of the same layer): same fp32 sums, one rounding.  Cout and Cin multiples of 32, else JG_ERR_UNSUPPORTED. */
+int jg_subpixel_fold_pair(int dtype, const float* w32, void* out, void* outT, int Cout, int Cin, jg_stream_t s);
 /* Four-phase (sub-pixel) form of a stride-2 TRANSPOSED convolution -- nn.ConvTranspose2d(k 3, stride 2, padding 1, output_padding 1) of the
  * ResnetDecoder tail (models/modules/segformer/segformer_generator.py:135-140) and the input gradient of the discriminators' Conv2d(k 4,
  * stride 2, padding 1) (models/modules/discriminators.py NLayerDiscriminator): wT = the flipped / transposed 16-bit working weights

@@ -22,7 +22,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
   X(HALO_DBG, 0) X(PERSIST64, 1) X(HALO_PIPE, 1) X(WGRAD_PIPE, 1) X(CONV_SPLITK, 1) X(CONV_SMALL_TILE, 1) X(GN_FUSED, 1)           \
   X(GN_FUSED_CAP, 256) X(GN_FUSED_DBG, 0) X(GN_FUSED_SLEEP, 4) X(WGRAD_LDS_PAD, 0) X(LN_BWD_CAP, 256) X(DW_BWD_CAP, 512)           \
   X(DW_BWD_PPT, 8) X(CONV_KXK, 1) X(CONV_RING, 1) X(WGRAD_DEEP, 1) X(WGRAD_SW, 0) X(DETERMINISTIC, 0) X(WGRAD_GROUP_BLOCKS, 1024)  \
-  X(SGEMM_SPLIT, 0) X(WGRAD_BIG, 1) X(DW_RUN, 1)
+  X(SGEMM_SPLIT, 0) X(WGRAD_BIG, 1) X(DW_RUN, 1) X(SUBPIXEL_DGRAD_CFG, 0)
 #define JG_TUNE_ENUM(name, dflt) JG_TUNE_##name,
 enum JgTune { JG_TUNE_LIST(JG_TUNE_ENUM) JG_TUNE_COUNT };
 #undef JG_TUNE_ENUM

@@ -26,6 +26,7 @@
 //   x_up 2   the same function in its sub-pixel form (PHASE instantiation below): 4 taps on folded weights per output phase
 //   res_up   the residual is at half resolution and is read through the same index map in the epilogue
 //   y_pool   the epilogue stores the 2x2 sum-pool of the tile (adjoint of x_up 1 when this launch computes an input gradient)
+//   y_pool 2 the same adjoint in its sub-pixel (gather) form: PHASE == 2 below, 16 instead of 36 tap-MACs per low-resolution pixel
 #include "conv_params.h"
 #include "conv_epilogue.h"
 #include "mfma_pipe.h"
@@ -67,12 +68,21 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // PIPE: the K loop in its software-pipelined form (mfma_pipe.h): the fragment reads of sub-step s + 1 (and, across the per-step barrier,
 // the pixel fragments of the next K-step -- the halo is stable for a whole chunk) are in flight under the MFMAs of sub-step s; only the
 // four weight-fragment reads that follow a barrier are exposed.  Same LDS images, same accumulators, bit-identical results.
-template <typename T, int BN, int NT, int WAVES_M, int WAVES_N, int NABUF, int NBBUF, int MINB, bool PHASE = false, int PIPE_MODE = 0>
+//
+// PHASE == 2 (GATHER): the adjoint of the sub-pixel form, i.e. the input gradient of conv3x3(Upsample_nearest(h)) w.r.t. h (y_mode 2).
+// x = dO [B, 2H, 2W, Cin] at the HIGH resolution, y = dh [B, H, W, N] at the low one; p.H / p.W are the low-resolution dimensions.  A
+// workgroup owns a 16x16 tile of low-resolution pixels and BN channels; its K loop runs over (64-channel chunk of dO, phase (py, px), 2x2
+// tap).  The 18x18 halo of a (chunk, phase) is the parity sub-image dO[2h' + py][2w' + px] (pixel stride 2 in both directions, fetched by
+// the same LDS-DMA rounds); tap (a, b) of phase (py, px) reads it at halo offset (2 - a - py, 2 - b - px) and all 16 K-steps of a chunk
+// accumulate into the same register tile.  Weights: [4][N][2][2][Cin] = the transpose of the forward's folded weights
+// (jg_subpixel_fold_pair).  With NABUF == 2 the next parity halo is fetched under the first three taps of the current one.
+template <typename T, int BN, int NT, int WAVES_M, int WAVES_N, int NABUF, int NBBUF, int MINB, int PHASE = 0, int PIPE_MODE = 0>
 __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
   constexpr int NTAP = PHASE ? 4 : 9;
   constexpr bool PIPE = PIPE_MODE != 0;
+  constexpr bool GATHER = PHASE == 2;
   static_assert(!PIPE || !PHASE, "the pipelined K loop covers the 9-tap form");
-  static_assert(!PHASE || NABUF == 1, "the phase form reloads its halo between chunks");
+  static_assert(PHASE != 1 || NABUF == 1, "the phase form reloads its halo between chunks");
   static_assert(!PHASE || NBBUF - 1 < NTAP, "weight ring prologue");
   constexpr int NWAVES = NT / 64;
   static_assert(WAVES_M * WAVES_N == NWAVES, "wave grid");
@@ -83,6 +93,8 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
   constexpr int B_BUF = BN * 8;
   static_assert(B_ROUNDS >= 1 && BN * 8 % NT == 0, "weight tile vs block size");
   static_assert(NABUF == 1 || A_ROUNDS <= 9, "halo prefetch is spread over the 9 taps");
+  constexpr int G_RPT = (A_ROUNDS + 2) / 3;        // GATHER, NABUF == 2: halo rounds of the next (chunk, phase) per tap, taps 0 .. 2
+  static_assert(!GATHER || NABUF == 1 || G_RPT <= 4, "vmcnt cases of the gather loop");
   static_assert(NBBUF >= 2 && NBBUF <= 5, "weight ring depth");
 
   // PIPE: the block's BN bias values are parked behind the ring (the pipelined loop has no registers to carry them across)
@@ -101,7 +113,7 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
     id = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
   }
   int py = 0, px = 0;
-  if constexpr (PHASE) {        // the four phases of a tile are neighbours in the id order: they share the halo in L2
+  if constexpr (PHASE == 1) {   // the four phases of a tile are neighbours in the id order: they share the halo in L2
     py = (id >> 1) & 1;
     px = id & 1;
     id >>= 2;
@@ -115,7 +127,7 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
   const int b = sp / (tw * th);
 
   const T* __restrict__ x = (const T*)p.x;
-  const T* __restrict__ w = (const T*)p.w + (PHASE ? (long)(py * 2 + px) * p.N * p.ldw : 0L);
+  const T* __restrict__ w = (const T*)p.w + (PHASE == 1 ? (long)(py * 2 + px) * p.N * p.ldw : 0L);
   const T* zp = reinterpret_cast<const T*>(&jg_halo_zero_page);
   typedef __attribute__((address_space(3))) char* lds_cptr;
   const unsigned lds0 = (unsigned)(size_t)(lds_cptr)(char*)&sm[0];   // LDS byte address of sm
@@ -137,6 +149,8 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
     const int kc = cpos ^ ((hx >> 1) & 7);   // swizzle by the COLUMN inside the halo row: the same for every row
     // x_up: the halo pixel (ih, iw) of the (virtual) upsampled image lives at (ih >> 1, iw >> 1) of the half-resolution tensor
     const int ush = p.x_up ? 1 : 0;
+    if constexpr (GATHER) aoff[rd] = ok ? (int)((((long)b * (2 * p.H) + 2 * ih) * (2 * p.W) + 2 * iw) * p.ldx) + kc * 8 : -1;   // phase (0, 0) of dO
+    else
     aoff[rd] = ok ? (int)((((long)b * (p.H >> ush) + (ih >> ush)) * (p.W >> ush) + (iw >> ush)) * p.ldx) + kc * 8 : -1;
   }
   int boff[B_ROUNDS];
@@ -149,10 +163,10 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
     boff[rd] = (n < p.N) ? (int)((long)n * p.ldw) + kc * 8 : -1;
   }
 
-  auto issue_a_round = [&](int abuf, int cc, int rd) {
+  auto issue_a_round = [&](int abuf, int cc, int rd) {     // GATHER: cc = element offset of the (chunk, phase) sub-image instead of the chunk index
     const int pos = rd * NT + tid;
     if (pos < HALO_CH) {
-      const T* src = aoff[rd] >= 0 ? x + aoff[rd] + cc * 64 : zp;
+      const T* src = aoff[rd] >= 0 ? x + aoff[rd] + (GATHER ? cc : cc * 64) : zp;
       glds16(src, lds0 + (abuf * HALO_CH + rd * NT + wave * 64) * 16);
     }
   };
@@ -205,7 +219,7 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
   };
 
   const int nch = p.Cin >> 6;       // 64-channel chunks
-  const int nk = nch * NTAP;
+  const int nk = nch * NTAP * (GATHER ? 4 : 1);
   static_assert(TN == 4, "one 64-channel epilogue pass per wave");
   float bias_pre[8];                // epilogue bias of this lane, in flight during the K loop
   float* sbias = reinterpret_cast<float*>(&sm[NABUF * HALO_CH + NBBUF * B_BUF]);
@@ -221,7 +235,7 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
     for (int rd = 0; rd < A_ROUNDS; ++rd) issue_a_round(0, 0, rd);
   }
 #pragma unroll
-  for (int pb = 0; pb < NBBUF - 1; ++pb) issue_b(pb, pb * p.Cin);   // taps 0 .. NBBUF-2 of chunk 0 (nk >= 9 always)
+  for (int pb = 0; pb < NBBUF - 1; ++pb) issue_b(pb, pb * p.Cin);   // taps 0 .. NBBUF-2 of chunk 0 (nk >= 9 always; PHASE: >= 4 > NBBUF - 2)
   wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
@@ -307,6 +321,62 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
     }
     // the last MFMAs are still in the pipe when the epilogue's first VALU reads the accumulators: the compiler does not see them
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+  } else if constexpr (GATHER) {
+    // stage hs = (chunk hs >> 2, phase hs & 3): one parity halo, four K-steps.  Sub-image offset in dO and weight-tile offset of a stage:
+    const int nhs = nch * 4;
+    auto a_off = [&](int hs) -> int { return (((hs >> 1) & 1) * (2 * p.W) + (hs & 1)) * (int)p.ldx + (hs >> 2) * 64; };
+    auto b_off = [&](int hs, int tap) -> int { return (hs & 3) * p.N * (int)p.ldw + tap * p.Cin + (hs >> 2) * 64; };
+    for (int hs = 0; hs < nhs; ++hs) {
+      const int abyte = (NABUF == 2 ? (hs & 1) : 0) * (HALO_CH * 16);
+      const bool next_stage = hs + 1 < nhs;
+      const int gy = (hs >> 1) & 1, gx = hs & 1;
+#pragma unroll
+      for (int tap = 0; tap < 4; ++tap) {
+        const bool b_iss = kpre < nk;
+        if (b_iss) {
+          int slot = bslot + NBBUF - 1;
+          if (slot >= NBBUF) slot -= NBBUF;
+          issue_b(slot, b_off(pre_cc, pre_tap));       // pre_cc counts stages here
+          ++kpre;
+          if (++pre_tap == 4) { pre_tap = 0; ++pre_cc; }
+        }
+        // G_RPT LDS-DMA rounds of the next stage's halo per tap, taps 0 .. 2 (wave-uniform count: the vmcnt below leaves them in flight)
+        int n_iss = 0;
+        if (NABUF == 2 && tap < 3 && next_stage && !(p.dbg & 4)) {
+          const int aof = a_off(hs + 1);
+#pragma unroll
+          for (int q = 0; q < G_RPT; ++q) {
+            const int rd = tap * G_RPT + q;
+            if (rd < A_ROUNDS && rd * NT + wave * 64 < HALO_CH) {
+              issue_a_round((hs + 1) & 1, aof, rd);
+              ++n_iss;
+            }
+          }
+        }
+        if (!(p.dbg & 2)) compute(abyte, (NABUF * HALO_CH + bslot * B_BUF) * 16, 2 - (tap >> 1) - gy, 2 - (tap & 1) - gx);
+        // the weight tile of the next K-step must have landed; at tap 3 also every halo round of the next stage (all issued at taps <= 2,
+        // i.e. before the youngest tile that may stay in flight)
+        if (NBBUF >= 3 && b_iss) {
+          constexpr int KEEP = (NBBUF - 2) * B_ROUNDS;
+          if (n_iss == 0) wait_vmcnt<KEEP>();
+          else if (n_iss == 1) wait_vmcnt<KEEP + 1>();
+          else if (n_iss == 2) wait_vmcnt<KEEP + 2>();
+          else if (n_iss == 3) wait_vmcnt<KEEP + 3>();
+          else wait_vmcnt<KEEP + 4>();
+        } else {
+          wait_vmcnt<0>();
+        }
+        __builtin_amdgcn_s_barrier();
+        if (++bslot == NBBUF) bslot = 0;
+      }
+      if (NABUF == 1 && next_stage) {
+        const int aof = a_off(hs + 1);
+#pragma unroll
+        for (int rd = 0; rd < A_ROUNDS; ++rd) issue_a_round(0, aof, rd);
+        wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+      }
+    }
   } else
   for (int cc = 0; cc < nch; ++cc) {
     const int abyte = (NABUF == 2 ? (cc & 1) : 0) * (HALO_CH * 16);
@@ -330,7 +400,7 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
       }
       // 3. MFMAs of this K-step
       if (!(p.dbg & 2)) {
-        if constexpr (PHASE) compute(abyte, (NABUF * HALO_CH + bslot * B_BUF) * 16, (tap >> 1) + py, (tap & 1) + px);
+        if constexpr (PHASE == 1) compute(abyte, (NABUF * HALO_CH + bslot * B_BUF) * 16, (tap >> 1) + py, (tap & 1) + px);
         else compute(abyte, (NABUF * HALO_CH + bslot * B_BUF) * 16, tap / 3, tap % 3);
       }
       // 4. the weight tile of the NEXT K-step (and, at tap 8, the whole next halo) must have landed;
@@ -364,12 +434,12 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
     for (int i = tid; i < BN * 2; i += NT) sred[i] = 0.f;
     __syncthreads();
   }
-  const long mrow0 = PHASE ? ((long)b * 2 * p.H + 2 * (oh0 + wm * TM) + py) * (2 * p.W) + 2 * ow0 + px
+  const long mrow0 = PHASE == 1 ? ((long)b * 2 * p.H + 2 * (oh0 + wm * TM) + py) * (2 * p.W) + 2 * ow0 + px
                            : ((long)b * p.H + oh0 + wm * TM) * p.W + ow0;
   // half-resolution residual (res_up): tile origins and the wave's row offset are even, so the nearest-upsample map is two shifts
   // (PHASE: the kernel's own grid IS the half resolution, the residual row of a pixel is its low-resolution index)
-  const int wres = PHASE ? p.W : (p.res_up ? (p.W >> 1) : p.W), rsh = (!PHASE && p.res_up) ? 1 : 0;
-  const long rrow0 = PHASE ? ((long)b * p.H + oh0 + wm * TM) * p.W + ow0
+  const int wres = PHASE == 1 ? p.W : (p.res_up ? (p.W >> 1) : p.W), rsh = (PHASE != 1 && p.res_up) ? 1 : 0;
+  const long rrow0 = PHASE == 1 ? ((long)b * p.H + oh0 + wm * TM) * p.W + ow0
                            : (p.res_up ? ((long)b * (p.H >> 1) + ((oh0 + wm * TM) >> 1)) * wres + (ow0 >> 1) : mrow0);
   if constexpr (PIPE) {
 #pragma unroll
@@ -379,9 +449,9 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
   for (int h = 0; h < TN / 4; ++h) {     // 64 output channels of the wave tile at a time
     jg_epilogue_lds<T, TM, true>(
         p, reinterpret_cast<f32x4(&)[4][TM]>(acc[4 * h]), smc + wave * 16384, lane, n0 + wn * WN + 64 * h, b,
-        [&](int lp) -> long { return PHASE ? mrow0 + (long)(lp >> 4) * (4 * p.W) + 2 * (lp & 15) : mrow0 + (long)(lp >> 4) * p.W + (lp & 15); },
+        [&](int lp) -> long { return PHASE == 1 ? mrow0 + (long)(lp >> 4) * (4 * p.W) + 2 * (lp & 15) : mrow0 + (long)(lp >> 4) * p.W + (lp & 15); },
         [&](int lp, long m) -> long {
-          if (PHASE && !p.res_up) return m;      // full-resolution residual: the output row itself
+          if (PHASE == 1 && !p.res_up) return m;      // full-resolution residual: the output row itself
           return rrow0 + (long)((lp >> 4) >> rsh) * wres + ((lp & 15) >> rsh);
         },
         [&](int slab, int r2, int c2) -> long {
@@ -407,7 +477,34 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
 template <typename T, int BN, int NT, int WMv, int WNv, int NABUF, int NBBUF, int MINB>
 void launch_halo_phase(const ConvP& p, hipStream_t st) {   // p.H / p.W: low-resolution grid; 4 phases per tile
   const int tiles = p.B * (p.H >> 4) * (p.W >> 4) * ((p.N + BN - 1) / BN) * 4;
-  hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN, NT, WMv, WNv, NABUF, NBBUF, MINB, true>), dim3(tiles), dim3(NT), 0, st, p);
+  hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN, NT, WMv, WNv, NABUF, NBBUF, MINB, 1>), dim3(tiles), dim3(NT), 0, st, p);
+}
+
+template <typename T, int BN, int NT, int WMv, int WNv, int NABUF, int NBBUF, int MINB>
+void launch_halo_gather(const ConvP& p, hipStream_t st) {  // p.H / p.W: low-resolution grid of the result; all four phases in one K loop
+  const int tiles = p.B * (p.H >> 4) * (p.W >> 4) * ((p.N + BN - 1) / BN);
+  hipLaunchKernelGGL((conv3x3_halo_kernel<T, BN, NT, WMv, WNv, NABUF, NBBUF, MINB, 2>), dim3(tiles), dim3(NT), 0, st, p);
+}
+
+// y_mode 2.  JG_SUBPIXEL_DGRAD_CFG 0: auto = the forward's tiles: 4 waves x (128 px x 64 ch), 128-wide, single halo buffer, two workgroups
+// per CU when N % 128 == 0, else the 64-wide tile; 1: the DOUBLE-buffered form for N % 128 == 0: two halo buffers + a 3-deep weight ring are
+// 129 KB, i.e. one workgroup per CU, so it runs 8 waves x (64 px x 64 ch).  Alone it is 5 - 19 % slower than the single-buffered tile (the
+// second workgroup of a CU hides a halo reload better than the prefetch does: 275 / 290 / 326 us against 253 / 243 / 312 us on the three
+// up-block layers), in the step 0.3 ms slower (profiles/subpixel_bwd.md); 2: the 64-wide tile for every shape.  With 4 waves two halo
+// buffers fit for no tile at two workgroups per CU (113 KB with the 128-wide ring, 105 KB with the 64-wide one).
+template <typename T>
+void dispatch_halo_gather(const ConvP& p, hipStream_t st) {
+  const int cfg = jg_tune(JG_TUNE_SUBPIXEL_DGRAD_CFG);
+  if (p.N % 128 == 0 && cfg == 1) {
+    jg_note_kernel("conv3x3_halo_kernel<subpixel dgrad,128-wide,8 waves>");
+    launch_halo_gather<T, 128, 512, 4, 2, 2, 3, 1>(p, st);
+  } else if (p.N % 128 == 0 && cfg == 0) {
+    jg_note_kernel("conv3x3_halo_kernel<subpixel dgrad,128-wide,4 waves>");
+    launch_halo_gather<T, 128, 256, 2, 2, 1, 2, 2>(p, st);
+  } else {
+    jg_note_kernel("conv3x3_halo_kernel<subpixel dgrad,64-wide>");
+    launch_halo_gather<T, 64, 256, 4, 1, 1, 3, 2>(p, st);
+  }
 }
 
 template <typename T, int BN, int NT, int WMv, int WNv, int NABUF, int NBBUF, int MINB, int PIPE = 0>
@@ -467,6 +564,37 @@ __global__ __launch_bounds__(256) void subpixel_fold_kernel(const float* __restr
   }
 }
 
+// Both folded tensors of a layer in one launch: out as above, and outT[ph][ci][a][b][co] = the same values transposed (the weights of the
+// sub-pixel input gradient, y_mode 2).  A block owns 16 co x 32 ci of one phase (blockIdx.y): the 9 fp32 taps go through LDS, so that both
+// tensors are written in runs (64 bytes along ci, 32 bytes along co).  The sums are taken in the order of subpixel_fold_kernel: `out` is
+// bit-identical to it.
+template <typename T>
+__global__ __launch_bounds__(256) void subpixel_fold_pair_kernel(const float* __restrict__ w32, T* __restrict__ out, T* __restrict__ outT, int Cout, int Cin) {
+  __shared__ float sw[16][9][33];
+  const int tci = Cin >> 5;
+  const int co0 = (blockIdx.x / tci) << 4, ci0 = (blockIdx.x % tci) << 5;
+  const int ph = blockIdx.y, py = ph >> 1, px = ph & 1;
+  for (int i = threadIdx.x; i < 16 * 9 * 32; i += 256) {
+    const int ci = i & 31, t = (i >> 5) % 9, co = i / (32 * 9);
+    sw[co][t][ci] = w32[((long)(co0 + co) * 9 + t) * Cin + ci0 + ci];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 16 * 32 * 4; i += 256) {
+#pragma unroll
+    for (int tr = 0; tr < 2; ++tr) {        // 0: out (ci fastest), 1: outT (co fastest)
+      const int co = tr ? (i & 15) : (i >> 7), ci = tr ? (i >> 6) : (i & 31), tap = tr ? (i >> 4) & 3 : (i >> 5) & 3;
+      const int a = tap >> 1, b = tap & 1;
+      const int r0 = (py == 0) ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2), r1 = (py == 0) ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2);
+      const int s0 = (px == 0) ? (b == 0 ? 0 : 1) : (b == 0 ? 0 : 2), s1 = (px == 0) ? (b == 0 ? 0 : 2) : (b == 0 ? 1 : 2);
+      float acc = 0.f;
+      for (int r = r0; r <= r1; ++r)
+        for (int sx = s0; sx <= s1; ++sx) acc += sw[co][r * 3 + sx][ci];
+      if (tr) outT[(((long)ph * Cin + ci0 + ci) * 4 + tap) * Cout + co0 + co] = from_f32<T>(acc);
+      else out[(((long)ph * Cout + co0 + co) * 4 + tap) * Cin + ci0 + ci] = from_f32<T>(acc);
+    }
+  }
+}
+
 // The same four-phase form for a TRANSPOSED convolution of stride 2 (the input gradient of a stride-2 convolution / nn.ConvTranspose2d):
 // y[2h + py][2w + px][n] = sum over (a, b) of Wp[py][px][n][a][b] . x[h + a + py - 1][w + b + px - 1], where tap (a, b) of phase (py, px) is tap
 // r = pad + 2 - py - 2a, s = pad + 2 - px - 2b of the strided convolution's kernel (zero outside 0 .. R-1: a 3x3 kernel fills 9 of the 16 slots, a
@@ -509,9 +637,31 @@ extern "C" int jg_subpixel_fold(int dtype, const float* w32, void* out, int Cout
   return JG_OK;
 }
 
+extern "C" int jg_subpixel_fold_pair(int dtype, const float* w32, void* out, void* outT, int Cout, int Cin, jg_stream_t s) {
+  if (!w32 || !out || !outT || Cout < 1 || Cin < 1) return JG_ERR_BAD_ARG;
+  if (Cout % 32 || Cin % 32 || (long)(Cout >> 4) * (Cin >> 5) >= (1L << 31)) return JG_ERR_UNSUPPORTED;
+  const int blocks = (Cout >> 4) * (Cin >> 5);
+  JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((subpixel_fold_pair_kernel<T>), dim3(blocks, 4), dim3(256), 0, (hipStream_t)s, w32, (T*)out, (T*)outT, Cout, Cin););
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+
 bool jg_conv_halo_try(int dtype, const ConvP& p0, int nbatch, hipStream_t st) {
   ConvP p = p0;
   p.dbg = jg_tune(JG_TUNE_HALO_DBG);
+  if (p.y_pool == 2) {
+    // sub-pixel input gradient: p.H / p.W arrive as the size of x = dO (the upsampled size); the kernel runs on the half-resolution grid of y.
+    // Shape limits of x_mode 2; every offset into dO and into the four weight slabs is a 32-bit element offset
+    if (nbatch != 1 || p.R != 3 || p.S != 3 || p.pad != 1 || p.stride != 1 || p.out_f32 || p.reflect || p.x_up || p.res_up) return false;
+    if (p.bias || p.res || p.stats) return false;
+    if (p.Cin % 64 || p.N % 64 || (p.H & 31) || (p.W & 31) || p.H != p.Ho || p.W != p.Wo || p.ldw != 4L * p.Cin) return false;
+    if ((long)p.B * p.H * p.W * p.ldx >= (1L << 31) || (long)4 * p.N * p.ldw >= (1L << 31)) return false;
+    p.H >>= 1; p.W >>= 1; p.y_pool = 0;
+    if (dtype == JG_F16) dispatch_halo_gather<f16_t>(p, st);
+    else if (dtype == JG_BF16) dispatch_halo_gather<bf16_t>(p, st);
+    else return false;
+    return true;
+  }
   if (p.x_up == 2) {
     // sub-pixel form: p.H / p.W arrive as the upsampled (output) size; the kernel runs on the half-resolution grid
     if (nbatch != 1 || p.R != 3 || p.S != 3 || p.pad != 1 || p.stride != 1 || p.out_f32 || p.reflect || p.y_pool) return false;

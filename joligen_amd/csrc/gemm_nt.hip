@@ -697,8 +697,9 @@ static int conv_args_to_params(const jg_conv_args* a, ConvP& p) {
   p.nslots = a->stats_slots > 0 ? a->stats_slots : 1;
   p.reflect = a->pad_mode == 1;
   if (a->pad_mode != 0 && a->pad_mode != 1) return JG_ERR_BAD_ARG;
-  p.y_pool = a->y_mode == 1;
-  if (a->y_mode != 0 && a->y_mode != 1) return JG_ERR_BAD_ARG;
+  p.y_pool = a->y_mode;      // 1: pooled store, 2: sub-pixel input gradient (w = the transposed folded weights of jg_subpixel_fold_pair)
+  if (a->y_mode < 0 || a->y_mode > 2) return JG_ERR_BAD_ARG;
+  if (a->y_mode == 2 && (a->x_mode || a->pad_mode || a->res_mode)) return JG_ERR_BAD_ARG;
   if (p.y_pool && (a->bias || a->res || a->stats || a->out_f32 || (a->Ho & 1) || (a->Wo & 1) || a->nbatch != 1)) return JG_ERR_BAD_ARG;
   p.x_up = a->x_mode;      // 1: upsample-on-read, 2: sub-pixel form (w = folded weights of jg_subpixel_fold)
   if (a->x_mode < 0 || a->x_mode > 2) return JG_ERR_BAD_ARG;

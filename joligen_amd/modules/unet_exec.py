@@ -64,6 +64,9 @@ FUSE_DOWN_POOL = os.environ.get("JG_FUSE_DOWN_POOL", "1") != "0"
 # forward of the up-block conv2 in its sub-pixel form (x_mode 2: 16 instead of 36 tap-MACs per low-resolution pixel)
 SUBPIXEL_CONV = os.environ.get("JG_SUBPIXEL_CONV", "1") != "0"
 POOL_IN_DGRAD = os.environ.get("JG_POOL_IN_DGRAD", "1") != "0"
+# input gradient of the same convolution in its sub-pixel form (y_mode 2: 16 instead of 36 tap-MACs per low-resolution pixel); taken where the
+# forward ran x_mode 2, on the transposed folded weights that the forward's fold launch writes alongside its own
+SUBPIXEL_DGRAD = os.environ.get("JG_SUBPIXEL_DGRAD", "1") != "0"
 X_UP_ON_READ = os.environ.get("JG_X_UP_ON_READ", "1") != "0"
 RES_UP_ON_READ = os.environ.get("JG_RES_UP_ON_READ", "1") != "0"
 FUSE_GN_REDUCE = os.environ.get("JG_FUSE_GN_REDUCE", "0") != "0"
@@ -166,6 +169,15 @@ def subpixel_fold(m, dtype):
     return out
 
 
+def subpixel_fold_pair(m, dtype):
+    """(folded weights [4][Cout][2][2][Cin], their transpose [4][Cin][2][2][Cout] for the sub-pixel input gradient) in one launch"""
+    out = torch.empty((4, m.Cout, 2, 2, m.Cin), device=m.weight.device, dtype=dtype)
+    outT = torch.empty((4, m.Cin, 2, 2, m.Cout), device=m.weight.device, dtype=dtype)
+    check(_lib.lib().jg_subpixel_fold_pair(_lib.JG_F16 if dtype == torch.float16 else _lib.JG_BF16, m.weight.data_ptr(), out.data_ptr(),
+                                           outT.data_ptr(), m.Cout, m.Cin, _st()), "jg_subpixel_fold_pair")
+    return out, outT
+
+
 def conv_fwd(x, m, out=None, res=None, res_scale=1.0, alpha=1.0, stats=None, res_up=False, x_up=False, wfold=None):
     B, H, W, Cin = x.shape
     if x_up:      # x is the half-resolution tensor, the convolution runs over its nearest upsample (jg_conv_args.x_mode 1)
@@ -199,7 +211,7 @@ def conv1x1_gn_apply(x, m, ab, act):
     return (yn, y) if ok is not False else None
 
 
-def conv_dgrad(dy, m, x_shape, out=None, res=None, alpha=1.0, gn=None, pool=None, pool_out=False):
+def conv_dgrad(dy, m, x_shape, out=None, res=None, alpha=1.0, gn=None, pool=None, pool_out=False, wfoldT=None):
     """Input gradient of a stride-1 convolution.  `gn = (x, ab, act)`: the result is the output-gradient of a
     GroupNorm with input x / coefficients ab; its backward reductions (sum du, sum du*x) are then taken in
     this epilogue and returned as `red` [B, NSLOT, C, 2] (None when the shape is not covered: the caller
@@ -211,6 +223,10 @@ def conv_dgrad(dy, m, x_shape, out=None, res=None, alpha=1.0, gn=None, pool=None
     if pool_out:   # the result is the 2x2 sum-pool of the input gradient (jg_conv_args.y_mode 1): adjoint of a conv over Upsample(h)
         assert out is None and res is None and gn is None
         out = torch.empty((B, H // 2, W // 2, Cin), device=dy.device, dtype=dy.dtype)
+        if wfoldT is not None:      # the same result from the sub-pixel form (jg_conv_args.y_mode 2) on the transposed folded weights
+            conv_nt(dy, wfoldT, out, B=B, H=Ho, W=Wo, Cin=Cout, Cout=Cin, R=3, S=3, pad=1, stride=1, Ho=H, Wo=W, ldx=_ld(dy), ldw=4 * Cout,
+                    ldy=_ld(out), alpha=alpha, y_mode=2)
+            return out
     if out is None:
         out = torch.empty(x_shape, device=dy.device, dtype=dy.dtype)
     red = None
@@ -627,10 +643,16 @@ class UNetExecutor:
         identity = isinstance(rb.skip_connection, nn.Identity)
         sk = xs if identity else (sk_pre if sk_pre is not None else conv_fwd(xs, rb.skip_connection.meta))
         out_t, out_st = dest(B, Ho, Wo, Cout)
-        wfold = subpixel_fold(c2m, h2.dtype) if (h2_up and SUBPIXEL_CONV and subpixel_ok(c2m, Ho, Wo)) else None
+        wfold = wfoldT = None
+        if h2_up and SUBPIXEL_CONV and subpixel_ok(c2m, Ho, Wo):
+            # the weights do not change between this step's forward and backward: the backward's transposed fold rides in the record
+            if SUBPIXEL_DGRAD and POOL_IN_DGRAD:
+                wfold, wfoldT = subpixel_fold_pair(c2m, h2.dtype)
+            else:
+                wfold = subpixel_fold(c2m, h2.dtype)
         conv_fwd(h2, c2m, out=out_t, res=sk, res_scale=skipw, stats=out_st, res_up=res_up, x_up=h2_up, wfold=wfold)
         rec = dict(kind="res", rb=rb, x=x, ab1=ab1, mr1=mr1, a1=a1, c1=c1, ab2=ab2, mr2=mr2, h2=h2, film=film,
-                   xs=None if identity else xs, skipw=skipw, identity=identity, low2=low2, h2_up=h2_up)
+                   xs=None if identity else xs, skipw=skipw, identity=identity, low2=low2, h2_up=h2_up, wfoldT=wfoldT)
         rec.update(self._in_fields(X))
         self.tape.append(rec)
         return Act(out_t, out_st, Ho * Wo, len(self.tape) - 1)
@@ -719,7 +741,7 @@ class UNetExecutor:
             full = (hb, 2 * hh, 2 * hw_, hc) if rec["h2_up"] else (hb, hh, hw_, hc)
             # adjoint of the upsample behind GroupNorm 2: pooled in the input-gradient epilogue when the halo kernel runs the layer
             if POOL_IN_DGRAD and halo_ok(c2m, full[1], full[2]):
-                dh2, red2 = conv_dgrad(dO, c2m, full, pool_out=True), None
+                dh2, red2 = conv_dgrad(dO, c2m, full, pool_out=True, wfoldT=rec.get("wfoldT")), None
             else:
                 dh2, red2 = pool2(conv_dgrad(dO, c2m, full), 1.0), None
         else:

@@ -162,6 +162,9 @@ def conv_nt(x, w, y, *, B, H, W, Cin, Cout, R, S, pad, stride, Ho, Wo, ldx, ldw,
         if x_mode == 2:    # sub-pixel form: 4 of the 9 tap-MACs per output pixel are executed -- count the MFMA work actually done
             KERNEL_TIMING.append((ran or "conv3x3_halo_kernel<subpixel>", ev0, ev1, 2.0 * B * Ho * Wo * Cout * 4 * Cin, (nbatch, B, Ho, Wo, Cin, Cout, 2),
                                   2.0 * nbatch * (B * (Ho // 2) * (Wo // 2) * Cin + B * Ho * Wo * Cout) + 2.0 * 16 * Cin * Cout))
+        elif y_mode == 2:  # sub-pixel input gradient: 16 tap-MACs per low-resolution pixel (4 per pixel of dO); dO read once, the low-resolution result written once
+            KERNEL_TIMING.append((ran or "conv3x3_halo_kernel<subpixel dgrad>", ev0, ev1, 2.0 * B * H * W * Cout * 4 * Cin, (nbatch, B, Ho, Wo, Cin, Cout, 2),
+                                  2.0 * nbatch * (B * H * W * Cin + B * (Ho // 2) * (Wo // 2) * Cout) + 2.0 * 16 * Cin * Cout))
         else:
             KERNEL_TIMING.append((ran or _conv_kernel_name(nbatch, H, W, Cin, Cout, R, S, pad, stride, B * Ho * Wo if (stats is None or (R == 3 and Cin == 8 and gn_reduce is None)) else 0), ev0, ev1,
                                   2.0 * nbatch * B * Ho * Wo * Cout * R * S * Cin, (nbatch, B, Ho, Wo, Cin, Cout, R),
