@@ -167,7 +167,14 @@ typedef struct {
   int32_t out_mode;
   float dbias_scale; /* dbias[co] += dbias_scale * sum_p dy[p][co]; 0 means 1 (a skip-path conv fed with skipw*dy) */
   int32_t pad_mode;  /* 1: x is read with mirrored borders (see jg_conv_args.pad_mode); same shape limits */
-  int32_t x_mode;    /* 1: x is the half-resolution tensor of jg_conv_args.x_mode 1 (H, W = the upsampled size); same shape limits */
+  /* x_mode 1: x is the half-resolution tensor of jg_conv_args.x_mode 1 (H, W = the upsampled size); same shape limits.
+   * x_mode 2: the same gradient in its sub-pixel form -- operands and result exactly those of x_mode 1 (no folded weights: dw is the
+   * ordinary [Cout][3][3][Cin_out] master gradient); the four parity planes of dy meet the zero-padded half-resolution x through 2x2
+   * taps and the 16 (phase, tap) sums are folded to the 9 taps before they are accumulated: the same 16-bit products as x_mode 1 in
+   * another fp32 summation order, 16 instead of 36 tap-MACs per pixel of x.  Halo-resident kernel only: 3x3, pad 1, stride 1, nbatch 1,
+   * JG_OUT_ATOMIC_F32, pad_mode 0, H and W multiples of 32, Cin and Cout multiples of 64, B * H * W * ldx and B * H * W * lddy below
+   * 2^31; JG_ERR_UNSUPPORTED (nothing launched) outside these limits.  jg_conv2d_wgrad_tn_group refuses every non-zero x_mode. */
+  int32_t x_mode;
 } jg_wgrad_args;
 int jg_conv2d_wgrad_tn(int dtype, const jg_wgrad_args* a, jg_stream_t stream);
 /* `n` <= 4096 independent weight-gradient problems (any geometry of jg_conv2d_wgrad_tn with nbatch 1, out_mode JG_OUT_ATOMIC_F32, pad_mode 0,

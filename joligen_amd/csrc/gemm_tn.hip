@@ -905,8 +905,8 @@ static int make_wgp(const jg_wgrad_args* a, WgP& p) {
   p.dbias_scale = a->dbias_scale != 0.f ? a->dbias_scale : 1.f;
   if (a->pad_mode != 0 && a->pad_mode != 1) return JG_ERR_BAD_ARG;
   p.reflect = a->pad_mode == 1;
-  if (a->x_mode != 0 && a->x_mode != 1) return JG_ERR_BAD_ARG;
-  p.x_up = a->x_mode == 1;
+  if (a->x_mode < 0 || a->x_mode > 2) return JG_ERR_BAD_ARG;
+  p.x_up = a->x_mode;
   if (p.x_up && (p.reflect || (a->H & 1) || (a->W & 1) || a->nbatch != 1)) return JG_ERR_BAD_ARG;
   return JG_OK;
 }
@@ -998,6 +998,11 @@ extern "C" int jg_conv2d_wgrad_tn(int dtype, const jg_wgrad_args* a, jg_stream_t
     if (rc != JG_OK) return rc;
   }
   const int variant = jg_tune(JG_TUNE_WGRAD_VARIANT);  // 1: register transpose; 2: transposing LDS reads; 3: 2 with 128-row tiles only; 4: + halo-resident 3x3
+  if (p.x_up == 2) {      // the sub-pixel form exists in the halo-resident 3x3 kernel alone
+    if (variant < 4 || !jg_wgrad_halo_try(dtype, p, a->nbatch, (hipStream_t)stream)) return JG_ERR_UNSUPPORTED;
+    JG_CHECK_LAUNCH();
+    return JG_OK;
+  }
   if (variant >= 4 && (jg_wgrad_halo_try(dtype, p, a->nbatch, (hipStream_t)stream) || jg_wgrad_kxk_try(dtype, p, a->nbatch, (hipStream_t)stream))) {
     JG_CHECK_LAUNCH();
     return JG_OK;

@@ -338,6 +338,251 @@ __global__ __launch_bounds__(WMR * 256, 3 - WMR) void wgrad3x3_halo_kernel(WgP p
   }
 }
 
+// Sub-pixel form of the x_mode 1 weight gradient (jg_wgrad_args.x_mode 2): x is the half-resolution tensor h, dy the gradient dO at the
+// upsampled size.  With dO_p[h'][w'] = dO[2h' + py][2w' + px] (the parity plane of phase p = (py, px)) and hpad = h with one ring of zeros,
+//
+//   dWp[py][px][a][b][co][ci] = sum_{b,h',w'} dO_p[h'][w'][co] * hpad[h' + a + py][w' + b + px][ci]        a, b in {0, 1}
+//   dw[r][s] = sum of the four dWp[py][px][a][b] whose fold sets contain r and s; per axis (phase, tap) -> taps:
+//              (0, 0) = {0}, (0, 1) = {1, 2}, (1, 0) = {0, 1}, (1, 1) = {2}
+//
+// 16 instead of 36 tap-MACs per low-resolution pixel: the same 16-bit products as x_mode 1 (a tap of x_mode 1 that reads a duplicate of
+// an h pixel is the product another tap already formed), summed in fp32 in another order.  A workgroup (8 waves, 64 co x one 64-channel
+// ci chunk) keeps the 16 (phase, tap) accumulators and walks a split-K slice of TL x 16 LOW-resolution tiles.  Per tile LDS-DMA brings in
+// the (TL + 2) x 18 zero-padded halo of h and the four parity planes of the 2 TL x 32 region of dO -- the DMA source address does the
+// de-interleave (pixel stride 2) -- each plane laid out like the dy tile above (pixel-major, fdy swizzle by the low-resolution column), so
+// the transposing fragment reads are those of the kernel above plus a plane offset.  A K-step is 32 pixels = two tile rows of one plane.
+// THREE tile buffers (3 x 45.5 KB): the DMA of tile t + 2 is issued right behind the barrier that opens tile t (every wave has left tile
+// t - 1, whose buffer it takes), so a tile costs ONE barrier and has two tiles of DMA in flight -- a tile is only 64 MFMAs per wave.
+// The 16 accumulators are folded to the 9 taps in registers, in a fixed order, before the atomics: one atomic per element of dw and
+// workgroup, as above.  LA: lookahead of the halo fragment ring in steps of the flat (sub-step, phase, tap) sequence (a step is 2 MFMAs;
+// 3 = 188 VGPRs, 5 = 200 and 2.5 % faster alone, the same in the step: profiles/subpixel_wgrad.md).
+template <typename T, int TL, int LA>
+__global__ __launch_bounds__(512, 1) void wgrad3x3_subpixel_kernel(WgP p, int ntiles, int per, int npairs, int ncot) {
+  constexpr int NT = 512, CPW = 2, BCO = 64;
+  constexpr int HW_ = 18, HPX = (TL + 2) * HW_;
+  constexpr int HALO_CH = HPX * 8;             // 16-byte chunks of the halo (64 channels = 128 B / pixel)
+  constexpr int DY_ROWB = BCO * 2;
+  constexpr int PL_CH = TL * 16 * 8;           // chunks of one parity plane
+  constexpr int A_ROUNDS = (HALO_CH + NT - 1) / NT, A_FULL = HALO_CH / NT;
+  constexpr int BUF_CH = HALO_CH + 4 * PL_CH;
+  constexpr int NSUB = TL / 2;                 // K-steps of 32 pixels (2 tile rows) per plane
+  static_assert(PL_CH == NT, "one DMA round per parity plane");
+  static_assert(A_ROUNDS - A_FULL <= 1, "at most one partial halo round");
+  static_assert(3 * BUF_CH * 16 <= 163840, "LDS per CU");
+  __shared__ uint4 sm[3 * BUF_CH];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+
+  int id;
+  {
+    const int nwg = gridDim.x;
+    const int q = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    id = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
+  }
+  const int pair = id % npairs, slice = id / npairs;
+  const int co0 = (pair % ncot) * BCO, ci0 = (pair / ncot) * 64;
+  const int t0 = slice * per;
+  const int t1 = min(ntiles, t0 + per);
+  if (t0 >= t1) return;
+
+  const T* __restrict__ xg = (const T*)p.x + ci0;
+  const T* __restrict__ dyg = (const T*)p.dy + co0;
+  const T* zp = reinterpret_cast<const T*>(&jg_wg_zero_page);
+  typedef __attribute__((address_space(3))) char* lds_cptr;
+  const unsigned lds0 = (unsigned)(size_t)(lds_cptr)(char*)&sm[0];
+  const char* smb = reinterpret_cast<const char*>(&sm[0]);
+  const int Hl = p.H >> 1, Wl = p.W >> 1;      // the low-resolution image
+  const int tw = Wl >> 4, th = Hl / TL;
+
+  // ---- per-thread LDS-DMA source coordinates relative to the tile origin ---------------------------
+  // a_yx: 16 bits per round, (valid << 15) | (hy << 8) | hx
+  int a_rel[A_ROUNDS];
+  unsigned a_yx = 0;
+  static_assert(A_ROUNDS <= 2, "halo coordinates of the DMA rounds share one register");
+#pragma unroll
+  for (int rd = 0; rd < A_ROUNDS; ++rd) {
+    const int pos = rd * NT + tid;
+    const int hp = pos >> 3, cpos = pos & 7;
+    const int hy = hp / HW_, hx = hp - hy * HW_;
+    const int chunk = (((cpos >> 1) ^ f4(hx)) << 1) | (cpos & 1);
+    a_rel[rd] = ((hy - 1) * Wl + (hx - 1)) * (int)p.ldx + chunk * 8;
+    a_yx |= (pos < HALO_CH ? (unsigned)(0x8000 | (hy << 8) | hx) : 0u) << (16 * rd);
+  }
+  // plane (py, px) of the tile: thread tid brings chunk cpos of low-resolution tile pixel (ty, xx) = dO[2 ty + py][2 xx + px]
+  int d_rel;
+  {
+    const int px = tid >> 3, cpos = tid & 7;
+    const int ty = px >> 4, xx = px & 15;
+    const int blk = (cpos >> 1) ^ fdy<BCO>(xx);
+    d_rel = (2 * ty * p.W + 2 * xx) * (int)p.lddy + ((blk << 1) | (cpos & 1)) * 8;
+  }
+
+  auto issue_tile = [&](int t, int buf) {
+    const int tx = t % tw;
+    const int r2 = t / tw;
+    const int ty = r2 % th;
+    const int b = r2 / th;
+    const int oh0 = ty * TL, ow0 = tx << 4;      // low-resolution tile origin
+    const T* xb = xg + (((long)b * Hl + oh0) * Wl + ow0) * p.ldx;
+    const T* db = dyg + (((long)b * p.H + 2 * oh0) * p.W + 2 * ow0) * p.lddy;
+    const unsigned l0 = lds0 + (buf * BUF_CH + wave * 64) * 16;
+    // the per-thread offsets pass through an opaque statement: hipcc otherwise hoists their 64-bit and unpacked forms out of the tile
+    // loop, six registers that the MFMA loop has no room for
+    int drel = d_rel;
+    unsigned yxp = a_yx;
+    asm volatile("" : "+v"(drel), "+v"(yxp));
+#pragma unroll
+    for (int pl = 0; pl < 4; ++pl)
+      glds16(db + drel + ((pl >> 1) * p.W + (pl & 1)) * (int)p.lddy, l0 + (HALO_CH + pl * PL_CH) * 16);
+#pragma unroll
+    for (int rd = 0; rd < A_ROUNDS; ++rd) {
+      const int yx = (int)(yxp >> (16 * rd)) & 0xFFFF;
+      if (yx & 0x8000) {
+        const int ih = oh0 - 1 + ((yx >> 8) & 127), iw = ow0 - 1 + (yx & 255);
+        const bool ok = (unsigned)ih < (unsigned)Hl && (unsigned)iw < (unsigned)Wl;
+        int rel = a_rel[rd];
+        asm volatile("" : "+v"(rel));
+        glds16(ok ? xb + rel : zp, l0 + rd * NT * 16);
+      }
+    }
+  };
+  // LDS-DMA instructions a wave issues per tile (wave-uniform): the count its vmcnt wait leaves in flight
+  const bool partial = (A_ROUNDS > A_FULL) && (A_FULL * NT + wave * 64 < HALO_CH);
+
+  // ---- fragment byte offsets inside the current buffer (plane 0, sub-step 0; halo offset (0, s3)) -------------
+  const int i16 = lane & 15, g = lane >> 4;
+  const int trow = g >> 1;
+  int abase[CPW][2], bbase[3][2];
+#pragma unroll
+  for (int rd = 0; rd < 2; ++rd) {
+    const int xq = (g & 1) * 8 + rd * 4 + (i16 >> 2);
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+      const int cb = wm * CPW + i;
+      abase[i][rd] = HALO_CH * 16 + (trow * 16 + xq) * DY_ROWB + ((cb ^ fdy<BCO>(xq)) << 5) + (i16 & 3) * 8;
+    }
+#pragma unroll
+    for (int s3 = 0; s3 < 3; ++s3) {
+      const int hx = xq + s3;
+      bbase[s3][rd] = (trow * HW_ + hx) * 128 + ((wn ^ f4(hx)) << 5) + (i16 & 3) * 8;
+    }
+  }
+  auto tr_frag = [&](int off0, int off1) -> uint4 {
+    const uint2 u0 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off0)));
+    const uint2 u1 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off1)));
+    return make_uint4(u0.x, u0.y, u1.x, u1.y);
+  };
+
+  // acc[((py * 2 + px) * 2 + a) * 2 + b]
+  f32x4 acc[16][CPW], accb[CPW];
+#pragma unroll
+  for (int k = 0; k < 16; ++k)
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) acc[k][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < CPW; ++i) accb[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const bool do_bias = p.dbias != nullptr && ci0 == 0 && wn == 0;
+  const uint32_t one1 = to_bits<T>(from_f32<T>(1.0f));
+  const uint32_t one2 = one1 | (one1 << 16);      // two 1.0 values: bf16 0x3F80, fp16 0x3C00
+
+  issue_tile(t0, 0);
+  if (t0 + 1 < t1) issue_tile(t0 + 1, 1);
+  int buf = 0;
+  for (int t = t0; t < t1; ++t) {
+    if (t + 1 < t1) {      // tile t + 1 stays in flight
+      if (partial) wait_vmcnt<4 + A_FULL + 1>(); else wait_vmcnt<4 + A_FULL>();
+    } else {
+      wait_vmcnt<0>();
+    }
+    __builtin_amdgcn_s_barrier();      // tile t has landed for every wave, and every wave has left tile t - 1
+    if (t + 2 < t1) issue_tile(t + 2, buf == 0 ? 2 : buf - 1);
+    {
+      // the flat sequence (sub-step, phase, tap): step = (sub * 4 + ph) * 4 + a * 2 + b
+      constexpr int NSTEP = NSUB * 16;
+      auto load_fb = [&](int step) -> uint4 {
+        const int sub = step >> 4, ph = (step >> 2) & 3, a = (step >> 1) & 1, b = step & 1;
+        const int row = 2 * sub + a + (ph >> 1), s3 = b + (ph & 1);
+        return tr_frag(bbase[s3][0] + row * (HW_ * 128), bbase[s3][1] + row * (HW_ * 128));
+      };
+      auto load_fa = [&](int grp, uint4 (&fa)[CPW]) {      // grp = sub * 4 + ph
+        const int off = ((grp & 3) * PL_CH * 16) + (grp >> 2) * 32 * DY_ROWB;
+#pragma unroll
+        for (int i = 0; i < CPW; ++i) fa[i] = tr_frag(abase[i][0] + off, abase[i][1] + off);
+      };
+      uint4 ring[LA + 1], fa[2][CPW];
+      load_fa(0, fa[0]);
+#pragma unroll
+      for (int s = 0; s < LA; ++s) ring[s] = load_fb(s);
+#pragma unroll
+      for (int step = 0; step < NSTEP; ++step) {
+        const int grp = step >> 2, tap = step & 3;
+        if (tap == 0 && do_bias) {      // in front of the lookahead read: the ones fragment sits in the ring slot that read is about to fill
+          // ... built here from a scalar the compiler cannot see through: kept across the loop it would hold four registers of its own
+          unsigned o2 = one2;
+          asm volatile("" : "+s"(o2));
+          const uint4 ones = make_uint4(o2, o2, o2, o2);
+#pragma unroll
+          for (int i = 0; i < CPW; ++i) jg_mfma_pinned<T>(accb[i], fa[grp & 1][i], ones);
+        }
+        if (step + LA < NSTEP) ring[(step + LA) % (LA + 1)] = load_fb(step + LA);
+        if (tap == 0 && grp + 1 < NSTEP / 4) load_fa(grp + 1, fa[(grp + 1) & 1]);      // dO fragments of the next (sub-step, phase): 4 steps ahead
+#pragma unroll
+        for (int i = 0; i < CPW; ++i) jg_mfma_pinned<T>(acc[(grp & 3) * 4 + tap][i], fa[grp & 1][i], ring[step % (LA + 1)]);
+      }
+      asm volatile("s_nop 7" ::: "memory");     // the compiler does not see the MFMAs: keep its next VALU write off their operands
+    }
+    // the fragment addresses move on to the next buffer in place (kept as running values: a base + buffer offset pair per address would
+    // cost ten more registers)
+    const int step_b = (buf == 2 ? -2 : 1) * (BUF_CH * 16);
+    buf = buf == 2 ? 0 : buf + 1;
+#pragma unroll
+    for (int rd = 0; rd < 2; ++rd) {
+#pragma unroll
+      for (int i = 0; i < CPW; ++i) abase[i][rd] += step_b;
+#pragma unroll
+      for (int s3 = 0; s3 < 3; ++s3) bbase[s3][rd] += step_b;
+    }
+  }
+  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");     // ... and its first read of the accumulators behind the last MFMA's write
+
+  // ---- epilogue: fold 16 -> 9 in registers (fixed order), D row = co = g*4 + q, col = ci = i16 -------------------
+  float* dw = (float*)p.dw;
+  const int ci = ci0 + wn * 16 + i16;
+  if (ci < p.Cin_out) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      // the two (phase, tap) of an axis whose fold sets contain tap r: {(0,0),(1,0)}, {(0,1),(1,0)}, {(0,1),(1,1)}
+      const int py0 = 0, a0 = r == 0 ? 0 : 1, py1 = 1, a1 = r == 2 ? 1 : 0;
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        const int px0 = 0, b0 = s == 0 ? 0 : 1, px1 = 1, b1 = s == 2 ? 1 : 0;
+#pragma unroll
+        for (int i = 0; i < CPW; ++i) {
+          const f32x4 v = ((acc[((py0 * 2 + px0) * 2 + a0) * 2 + b0][i] + acc[((py0 * 2 + px1) * 2 + a0) * 2 + b1][i]) +
+                           (acc[((py1 * 2 + px0) * 2 + a1) * 2 + b0][i] + acc[((py1 * 2 + px1) * 2 + a1) * 2 + b1][i]));
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int co = co0 + (wm * CPW + i) * 16 + g * 4 + q;
+            if (co < p.Cout_out) atomicAdd(dw + (long)co * p.lddw + (long)(r * 3 + s) * p.Cin_out + ci, p.alpha * v[q]);
+          }
+        }
+      }
+    }
+  }
+  if (do_bias && i16 == 0) {
+#pragma unroll
+    for (int i = 0; i < CPW; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int co = co0 + (wm * CPW + i) * 16 + g * 4 + q;
+        if (co < p.Cout_out) atomicAdd(p.dbias + co, p.dbias_scale * accb[i][q]);
+      }
+  }
+}
+
 // Split-K choice: `slots` workgroups run at a time (1 or 2 per CU by LDS), so the launch runs in rounds; every block
 // walks `per` tiles and pays a fixed prologue + atomic epilogue worth about OVH tiles.
 static void pick_split(int npairs, int ntiles, int ovh, int slots, int* per_out, int* splitk_out) {
@@ -373,6 +618,19 @@ void launch_wg(const WgP& p, hipStream_t st) {
   const size_t pad = (size_t)jg_tune(JG_TUNE_WGRAD_LDS_PAD);
   if (pipe) hipLaunchKernelGGL((wgrad3x3_halo_kernel<T, TH, CPW, WMR, XMODE, CPW == 2>), dim3(npairs * splitk), dim3(WMR * 256), pad, st, p, ntiles, per, npairs, ncot, jg_tune(JG_TUNE_HALO_DBG));
   else hipLaunchKernelGGL((wgrad3x3_halo_kernel<T, TH, CPW, WMR, XMODE>), dim3(npairs * splitk), dim3(WMR * 256), pad, st, p, ntiles, per, npairs, ncot, jg_tune(JG_TUNE_HALO_DBG));
+}
+
+// x_mode 2: 4-row x 16 low-resolution tiles, 64 co, one workgroup per CU (three 45.5 KB tile buffers)
+template <typename T>
+void launch_subpixel(const WgP& p, hipStream_t st) {
+  constexpr int TL = 4;
+  const int ncot = p.Cout / 64, npairs = ncot * (p.Cin / 64);
+  const int ntiles = p.B * ((p.H >> 1) / TL) * (p.W >> 5);
+  int per, splitk;
+  // a tile is 64 MFMAs per wave (144 in the 16-row tile, whose prologue + atomic epilogue are worth 6 of its tiles)
+  pick_split(npairs, ntiles, 14, 256, &per, &splitk);
+  jg_note_kernel("wgrad3x3_halo_kernel<subpixel,4 rows,64 co>");
+  hipLaunchKernelGGL((wgrad3x3_subpixel_kernel<T, TL, 3>), dim3(npairs * splitk), dim3(512), 0, st, p, ntiles, per, npairs, ncot);
 }
 
 template <typename T>
@@ -421,6 +679,14 @@ bool jg_wgrad_halo_try(int dtype, const WgP& p, int nbatch, hipStream_t st, bool
   if (p.Cin % 64 || (p.Cout % 64 && (p.Cout > 64 || (p.Cout & 7))) || (p.H & 15) || (p.W & 15) || p.H != p.Ho || p.W != p.Wo) return false;
   if (p.Cout < 64 && ((long)p.B * p.H * p.W < 262144 || p.reflect || p.x_up)) return false;      // small launches stay on the im2col kernel
   if ((long)p.B * p.H * p.W * p.ldx >= (1L << 31) || (long)p.B * p.H * p.W * p.lddy >= (1L << 31)) return false;
+  if (p.x_up == 2) {      // the sub-pixel form: the forward's shape limits (jg_conv_args.x_mode 2); no other kernel serves it
+    if (p.reflect || (p.H & 31) || (p.W & 31) || p.Cout % 64) return false;
+    if (dry_run) return dtype == JG_F16 || dtype == JG_BF16;
+    if (dtype == JG_F16) launch_subpixel<f16_t>(p, st);
+    else if (dtype == JG_BF16) launch_subpixel<bf16_t>(p, st);
+    else return false;
+    return true;
+  }
   if (dry_run) return dtype == JG_F16 || dtype == JG_BF16;
   if (dtype == JG_F16) dispatch_wg<f16_t>(p, st);
   else if (dtype == JG_BF16) dispatch_wg<bf16_t>(p, st);

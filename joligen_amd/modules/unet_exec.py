@@ -67,6 +67,9 @@ POOL_IN_DGRAD = os.environ.get("JG_POOL_IN_DGRAD", "1") != "0"
 # input gradient of the same convolution in its sub-pixel form (y_mode 2: 16 instead of 36 tap-MACs per low-resolution pixel); taken where the
 # forward ran x_mode 2, on the transposed folded weights that the forward's fold launch writes alongside its own
 SUBPIXEL_DGRAD = os.environ.get("JG_SUBPIXEL_DGRAD", "1") != "0"
+# weight gradient of the same convolution in its sub-pixel form (jg_wgrad_args.x_mode 2: 16 instead of 36 tap-MACs per low-resolution pixel); no
+# folded weights are involved, so it does not depend on what the forward ran.  Taken where x is read through the upsample map and subpixel_ok.
+SUBPIXEL_WGRAD = os.environ.get("JG_SUBPIXEL_WGRAD", "1") != "0"
 X_UP_ON_READ = os.environ.get("JG_X_UP_ON_READ", "1") != "0"
 RES_UP_ON_READ = os.environ.get("JG_RES_UP_ON_READ", "1") != "0"
 FUSE_GN_REDUCE = os.environ.get("JG_FUSE_GN_REDUCE", "0") != "0"
@@ -241,7 +244,8 @@ def conv_dgrad(dy, m, x_shape, out=None, res=None, alpha=1.0, gn=None, pool=None
     return (out, red) if gn is not None else out
 
 
-def conv_wgrad(dy, x, m, alpha=1.0, dbias_scale=0.0, x_up=False):
+def conv_wgrad(dy, x, m, alpha=1.0, dbias_scale=0.0, x_up=False, subpixel=False):
+    """`subpixel` (with x_up): jg_wgrad_args.x_mode 2, the same gradient from the four parity planes of dy"""
     B, H, W, Cin = x.shape
     if x_up:
         H, W = 2 * H, 2 * W
@@ -254,7 +258,7 @@ def conv_wgrad(dy, x, m, alpha=1.0, dbias_scale=0.0, x_up=False):
     splitk = ops._wgrad_splitk(tiles, B * Ho * Wo)
     wgrad_tn(dy, x, wg, B=B, H=H, W=W, Cin=Cin, Cout=Cout, R=m.R, S=m.S, pad=m.pad, stride=m.stride, Ho=Ho, Wo=Wo,
              lddy=_ld(dy), ldx=_ld(x), lddw=m.R * m.S * m.Cin_real, dbias=m.bias.grad if m.bias is not None else None,
-             Cin_out=m.Cin_real, Cout_out=m.Cout_real, splitk=splitk, alpha=alpha, dbias_scale=dbias_scale, x_mode=1 if x_up else 0)
+             Cin_out=m.Cin_real, Cout_out=m.Cout_real, splitk=splitk, alpha=alpha, dbias_scale=dbias_scale, x_mode=(2 if subpixel else 1) if x_up else 0)
 
 
 def gn_coef(st, hw, gamma, beta, film, G, eps):
@@ -734,8 +738,9 @@ class UNetExecutor:
         gn2, c2m = rb.out_layers[0].norm, rb.out_layers[3].meta
         skipw = rec["skipw"]
         # conv2
+        sp_wg = rec["h2_up"] and SUBPIXEL_WGRAD and subpixel_ok(c2m, dO.shape[1], dO.shape[2])
         if WGRAD_FIRST:
-            self.wgrad(dO, rec["h2"], c2m, x_up=rec["h2_up"])
+            self.wgrad(dO, rec["h2"], c2m, x_up=rec["h2_up"], subpixel=sp_wg)
         if rec.get("low2"):
             hb, hh, hw_, hc = rec["h2"].shape
             full = (hb, 2 * hh, 2 * hw_, hc) if rec["h2_up"] else (hb, hh, hw_, hc)
@@ -747,7 +752,7 @@ class UNetExecutor:
         else:
             dh2, red2 = conv_dgrad(dO, c2m, rec["h2"].shape, gn=(rec["c1"], rec["ab2"], JG_ACT_SILU), pool=self.bpool)
         if not WGRAD_FIRST:
-            self.wgrad(dO, rec["h2"], c2m, x_up=rec["h2_up"])
+            self.wgrad(dO, rec["h2"], c2m, x_up=rec["h2_up"], subpixel=sp_wg)
         # GroupNorm 2 (+FiLM +SiLU)
         off, n = rb.emb_slice
         dc1 = gn_bwd(rec["c1"], dh2, rec["ab2"], rec["mr2"], gn2.weight, gn2.bias, rec["film"], gn2.num_groups, JG_ACT_SILU,

@@ -208,7 +208,8 @@ def wgrad_tn(dy, x, dw, *, B, H, W, Cin, Cout, R, S, pad, stride, Ho, Wo, lddy, 
     if KERNEL_TIMING is not None:
         ev1.record()
         KERNEL_TIMING.append((_lib.lib().jg_last_kernel().decode() or _wgrad_kernel_name(nbatch, H, W, Cin, Cout, R, S, pad, stride, out_mode), ev0, ev1,
-                              2.0 * nbatch * B * Ho * Wo * Cout * R * S * Cin, (nbatch, B, Ho, Wo, Cin, Cout, R, splitk),
+                              # x_mode 2 (sub-pixel form): 16 of the 36 tap-MACs per low-resolution pixel are executed -- the MFMA work actually done
+                              2.0 * nbatch * B * Ho * Wo * Cout * (4 if x_mode == 2 else R * S) * Cin, (nbatch, B, Ho, Wo, Cin, Cout, R, splitk),
                               2.0 * nbatch * (B * H * W * Cin + B * Ho * Wo * Cout) + 4.0 * R * S * Cin * Cout))
 
 
