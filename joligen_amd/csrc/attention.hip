@@ -18,9 +18,6 @@
 
 namespace {
 
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
-
 constexpr int D = 32;        // head dim
 constexpr int BQ = 128;      // rows per block (queries, or keys in the dK/dV kernel)
 constexpr int BK = 128;      // streamed rows per chunk

@@ -10,6 +10,9 @@ typedef __bf16 bf16_t;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+// value and LDS pointer type of the transposing LDS read ds_read_b64_tr_b16 (__builtin_amdgcn_ds_read_tr16_b64_v4i16)
+typedef short s16x4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
 
 #define JG_WAVE 64
 

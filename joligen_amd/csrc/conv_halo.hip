@@ -30,6 +30,7 @@
 #include "conv_params.h"
 #include "conv_epilogue.h"
 #include "mfma_pipe.h"
+#include "lds_dma.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -38,26 +39,9 @@ namespace {
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-__device__ uint4 jg_halo_zero_page = {0u, 0u, 0u, 0u};
-
-constexpr int HW_ = 18;                 // halo width / height
+constexpr int HW_ = 18;                // halo width / height
 constexpr int HALO_PX = HW_ * HW_;      // 324
 constexpr int HALO_CH = HALO_PX * 8;    // 16-byte chunks per halo buffer
-
-// LDS-DMA issued from inline asm: hipcc does not model it, so it neither drains it with a
-// vmcnt(0) before the next ds_read (what it does for __builtin_amdgcn_global_load_lds) nor counts
-// it -- every wait on these loads is an explicit wait_vmcnt<N>() below.  M0 (the LDS destination
-// base) is compiler-reserved: saved, written and restored inside the one statement
-// (cdna_hip_programming.md 5.7).
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // PHASE (sub-pixel form of conv3x3 over a nearest-x2-upsampled input, x_mode 2): p.H / p.W are the LOW-resolution dimensions of x,
 // y is [B, 2H, 2W, N].  A workgroup owns a 16x16 tile of low-resolution pixels, BN channels and ONE of the four output phases
@@ -106,12 +90,7 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
   // ---- block -> (image, tile row, tile col, channel tile); XCD-aware: consecutive ids share an L2 ----
-  const int nwg = gridDim.x;
-  int id;
-  {
-    const int q = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    id = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
-  }
+  int id = xcd_block_id();
   int py = 0, px = 0;
   if constexpr (PHASE == 1) {   // the four phases of a tile are neighbours in the id order: they share the halo in L2
     py = (id >> 1) & 1;
@@ -128,7 +107,7 @@ __global__ __launch_bounds__(NT, MINB) void conv3x3_halo_kernel(ConvP p) {
 
   const T* __restrict__ x = (const T*)p.x;
   const T* __restrict__ w = (const T*)p.w + (PHASE == 1 ? (long)(py * 2 + px) * p.N * p.ldw : 0L);
-  const T* zp = reinterpret_cast<const T*>(&jg_halo_zero_page);
+  const T* zp = reinterpret_cast<const T*>(&jg_zero_page);
   typedef __attribute__((address_space(3))) char* lds_cptr;
   const unsigned lds0 = (unsigned)(size_t)(lds_cptr)(char*)&sm[0];   // LDS byte address of sm
   const char* smb = reinterpret_cast<const char*>(&sm[0]);

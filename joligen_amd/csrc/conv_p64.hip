@@ -24,6 +24,7 @@
 // else (upsample-on-read, pooled stores, reflect padding, reduction mode, fp32 output) stays on conv_halo.hip.
 #include "conv_params.h"
 #include "conv_epilogue.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -32,15 +33,6 @@ constexpr int HALO_CH = HW_ * HW_ * 8;     // 2592 16-byte chunks per halo buffe
 constexpr int W_CH = 64 * 9 * 8;           // 4608 chunks: [tap][row][8]
 constexpr int REGION = HALO_CH / 4;        // 648 chunks of a halo buffer are loaded (and later used as scratch) by one wave
 constexpr int A_RD = (REGION + 63) / 64;   // 11 LDS-DMA rounds per wave and tile
-
-__device__ uint4 jg_p64_zero_page = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct TileRef { int b, oh0, ow0, sp; };
 
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_p64_kernel(ConvP p, int nsp, i
 
   const T* __restrict__ x = (const T*)p.x;
   const T* __restrict__ wt = (const T*)p.w;
-  const T* zp = reinterpret_cast<const T*>(&jg_p64_zero_page);
+  const T* zp = reinterpret_cast<const T*>(&jg_zero_page);
   typedef __attribute__((address_space(3))) char* lds_cptr;
   const unsigned lds0 = (unsigned)(size_t)(lds_cptr)(char*)&sm[0];
   char* smc = reinterpret_cast<char*>(&sm[0]);

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "conv_params.h"
 #include "conv_epilogue.h"
+#include "lds_dma.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -195,20 +196,12 @@ __global__ __launch_bounds__(256) void conv_nt_kernel(ConvP p) {
 // wave-base + lane*16, i.e. LDS stays LINEAR in issue order; the bank swizzle therefore goes on the
 // SOURCE side: the lane that lands on physical chunk position c of row r fetches the logical
 // k-chunk c ^ swz(r) (cdna_hip_programming.md 5.4 rule 21).  Zero padding / ragged edges: invalid
-// lanes fetch from a 16-byte device-global zero page (always a valid address).
+// lanes fetch from the 16-byte device-global zero page of lds_dma.h (always a valid address).
 // BK = 32 (64-byte rows, swz64) or 64 (128-byte rows, swz128).
-__device__ uint4 jg_zero_page = {0u, 0u, 0u, 0u};
-
 __device__ __forceinline__ int swz128r(int row) { return (row >> 1) & 7; }
 
-// LDS-DMA from inline asm (as conv_halo.hip): hipcc neither drains nor counts it, which is what lets the ring form below keep NST - 1
-// stages in flight across its one raw s_barrier per K step; every wait on these loads is an explicit wait_vmcnt_nt<N>().
-__device__ __forceinline__ void glds16_nt(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt_nt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// The ring form below issues its LDS-DMA from inline asm (glds16, lds_dma.h): hipcc neither drains nor counts it, which is what keeps
+// NST - 1 stages in flight across the one raw s_barrier per K step; every wait on these loads is an explicit wait_vmcnt<N>().
 
 // NST = 2: double buffer, one drain + __syncthreads per K step (many co-resident workgroups hide the L2 -> LDS latency between them).
 // NST > 2 (round 5): a ring of NST stages with NST - 1 K steps in flight per workgroup and a counted wait -- for the launches whose grid
@@ -232,14 +225,9 @@ __global__ __launch_bounds__(256) void conv_nt_glds_kernel(ConvP p) {
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
   const int tilesN = (p.N + BN - 1) / BN;
-  // XCD-aware tile order (round 6; conv_halo.hip has had it since round 2): workgroup b runs on XCD b % 8, so with the plain order the tilesN
-  // column tiles of one row block -- which read the SAME rows of x -- sat in different L2s and x crossed HBM tilesN times (PMC: 1.49 x the
-  // algorithmic bytes on the 128 x 128 tile).  Each XCD now owns a contiguous run of tile ids: neighbours in n (and, for R > 1, in m) share an L2.
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r8 = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
-  }
+  // XCD-aware tile order (lds_dma.h): the tilesN column tiles of one row block read the SAME rows of x; neighbours in n (and, for R > 1,
+  // in m) share an L2
+  const int bid = xcd_remap((int)blockIdx.x, gridDim.x);
   const int n0 = (bid % tilesN) * BN;
   const int m0 = (bid / tilesN) * BM;
 
@@ -343,12 +331,12 @@ __global__ __launch_bounds__(256) void conv_nt_glds_kernel(ConvP p) {
       for (int i = 0; i < A_CH; ++i) {
         const int ih = ih0[i] + r, iw = iw0[i] + s;
         const bool ok = kvalid && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-        glds16_nt(ok ? x + (((long)(pb[i] + ih) * p.W + iw) * p.ldx + c) : zp, dst + 256 * 16 * i);
+        glds16(ok ? x + (((long)(pb[i] + ih) * p.W + iw) * p.ldx + c) : zp, dst + 256 * 16 * i);
       }
 #pragma unroll
       for (int i = 0; i < B_CH; ++i) {
         const int n = n0 + srow + RSTEP * i;
-        glds16_nt((kvalid && n < p.N) ? w + ((long)n * p.ldw + kg) : zp, dst + (BM * CPR + 256 * i) * 16);
+        glds16((kvalid && n < p.N) ? w + ((long)n * p.ldw + kg) : zp, dst + (BM * CPR + 256 * i) * 16);
       }
       if (live) advance_k();
     };
@@ -356,18 +344,18 @@ __global__ __launch_bounds__(256) void conv_nt_glds_kernel(ConvP p) {
     for (int st = 0; st < NST - 1; ++st) issue_ring(st, st < nk);
     int cur = 0, nxt = NST - 1;
     for (int ks = 0; ks < nk; ++ks) {
-      wait_vmcnt_nt<(NST - 2) * LPS>();               // stage ks has landed (this thread's share) ...
+      wait_vmcnt<(NST - 2) * LPS>();                  // stage ks has landed (this thread's share) ...
       __builtin_amdgcn_s_barrier();                   // ... everybody's has, and everybody is done reading stage ks - 1
       issue_ring(nxt, ks + NST - 1 < nk);             // = the buffer of stage ks - 1
       compute(cur);
       cur = cur + 1 == NST ? 0 : cur + 1;
       nxt = nxt + 1 == NST ? 0 : nxt + 1;
     }
-    wait_vmcnt_nt<0>();                               // the epilogue below may reuse the ring as scratch
+    wait_vmcnt<0>();                                  // the epilogue below may reuse the ring as scratch
     __builtin_amdgcn_s_barrier();
   } else {
   if (nk > 0) issue_loads(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __syncthreads();
   for (int ks = 0; ks < nk; ++ks) {
     const int cur = ks & 1;
@@ -376,7 +364,7 @@ __global__ __launch_bounds__(256) void conv_nt_glds_kernel(ConvP p) {
       issue_loads(cur ^ 1);
     }
     compute(cur);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
   }
   }

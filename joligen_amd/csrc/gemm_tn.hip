@@ -14,6 +14,7 @@
 // ds_read_b128 groups and the 16-lane ds_write_b64 groups.
 #include "common.h"
 #include "wgrad_params.h"
+#include "lds_dma.h"
 #include <vector>
 #include <cstdlib>
 
@@ -231,7 +232,6 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(WgP p) {
 // k-values of a 16x16x32 operand; A and B use the same pixel<->k assignment, which is all the MFMA
 // needs.  The 32-byte (16-channel) block index of a row is XOR-swizzled with row bits {0,1,3} so a
 // 32-lane service group of the transposing read touches all 64 banks exactly once.
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int swz_tr(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
 
 // WAVES_M = 2: block tile 128 (co) x 128, waves 2x2 of 64x64.  WAVES_M = 1: block tile 64 (co) x 128,
@@ -347,7 +347,6 @@ __device__ __forceinline__ void wgrad_tn_tr_body(const WgP& p, const int bx, con
     for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int i16 = lane & 15, g = lane >> 4;
-  typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
   auto frag = [&](int buf, int tile, int cb, int sub) -> uint4 {
     const char* base = reinterpret_cast<const char*>(&sm[buf][tile]);
     uint32_t w[4];
@@ -460,8 +459,7 @@ __device__ __forceinline__ void wgrad_tn_tr_body(const WgP& p, const int bx, con
 // read per launch for 100 MB of operands).  Each XCD now owns a contiguous run of the slice-major ids: all tiles of a slice share an L2.
 __device__ __forceinline__ void wgrad_xcd_order(int& bx, int& bz) {
   const int tiles = gridDim.x, nwg = tiles * gridDim.z, lin = blockIdx.x + blockIdx.z * tiles;
-  const int q = nwg >> 3, r8 = nwg & 7, xcd = lin & 7, idx = lin >> 3;
-  const int id = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
+  const int id = xcd_remap(lin, nwg);
   bx = id % tiles;
   bz = id / tiles;
 }
@@ -567,7 +565,6 @@ __device__ __forceinline__ void wgrad_tn_big_body(const WgP& p, const int bx, co
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int i16 = lane & 15, g = lane >> 4;
-  typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
   auto frag = [&](int buf, int tile, int cb, int sub) -> uint4 {
     const char* base = reinterpret_cast<const char*>(&sm[buf][tile]);
     uint32_t w[4];
@@ -654,12 +651,6 @@ __device__ __forceinline__ void wgrad_tn_big_body(const WgP& p, const int bx, co
 // are in flight under the MFMAs of step k, and the loop has ONE barrier per step (the wait for this wave's loads, then the barrier, tell
 // every wave both that buffer `cur` is complete and that nobody reads `cur ^ 1` any more).  The bias gradient comes from the dy fragments
 // through an MFMA with a ones operand (wgrad_kxk.hip).
-__device__ uint4 jg_wt_zero_page = {0u, 0u, 0u, 0u};
-__device__ __forceinline__ void glds16_tn(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 // SPREAD: one DMA per 8 MFMAs instead of the burst after the barrier -- measured equal (292.9 vs 292.2 us at 128 K steps per workgroup): off
 template <typename T, bool SPREAD = false, int ABL = 0>      // ABL (timing only, wrong results): 1 = no MFMAs, 2 = no fragment reads, 3 = no DMA
 __device__ __forceinline__ void wgrad_tn_dma_body(const WgP& p, const int bx, const int bz, uint4 (*sm)[2 * BIG_TILE]) {
@@ -676,7 +667,7 @@ __device__ __forceinline__ void wgrad_tn_dma_body(const WgP& p, const int bx, co
   const int zb = batch / p.nh, zh = batch % p.nh;
   const T* __restrict__ dy = (const T*)p.dy + zb * p.sdyb + zh * p.sdyh;
   const T* __restrict__ x = (const T*)p.x + zb * p.sxb + zh * p.sxh;
-  const T* zp = reinterpret_cast<const T*>(&jg_wt_zero_page);
+  const T* zp = reinterpret_cast<const T*>(&jg_zero_page);
 
   int per = (p.Mpix + p.splitk - 1) / p.splitk;
   per = (per + BK - 1) / BK * BK;
@@ -712,7 +703,7 @@ __device__ __forceinline__ void wgrad_tn_dma_body(const WgP& p, const int bx, co
     const int pp = kbase + ((rd * 512 + tid) >> 5);
     if (idx < 4) {
       const bool ok = a_ok[rd] && pp < kend;
-      glds16_tn(ok ? dy + (long)pp * p.lddy + a_col[rd] : zp, l0 + rd * 512 * 16);
+      glds16(ok ? dy + (long)pp * p.lddy + a_col[rd] : zp, l0 + rd * 512 * 16);
     } else {
       const int ow = pp % p.Wo;
       const int t = pp / p.Wo;
@@ -721,7 +712,7 @@ __device__ __forceinline__ void wgrad_tn_dma_body(const WgP& p, const int bx, co
       const int ih = oh * p.stride + b_fr[rd] - p.pad;
       const int iw = ow * p.stride + b_fs[rd] - p.pad;
       const bool ok = b_ok[rd] && pp < kend && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-      glds16_tn(ok ? x + ((long)(b * p.H + ih) * p.W + iw) * p.ldx + b_ci[rd] : zp, l0 + (BIG_TILE + rd * 512) * 16);
+      glds16(ok ? x + ((long)(b * p.H + ih) * p.W + iw) * p.ldx + b_ci[rd] : zp, l0 + (BIG_TILE + rd * 512) * 16);
     }
   };
   auto issue = [&](int kbase, int buf) {
@@ -742,7 +733,6 @@ __device__ __forceinline__ void wgrad_tn_dma_body(const WgP& p, const int bx, co
   const uint4 ones = make_uint4(one2, one2, one2, one2);
 
   const int i16 = lane & 15, g = lane >> 4;
-  typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
   auto frag = [&](int buf, int tile, int cb, int sub) -> uint4 {
     if constexpr (ABL == 2) return make_uint4((unsigned)(buf + tile), (unsigned)cb, (unsigned)sub, (unsigned)lane);
     const char* base = reinterpret_cast<const char*>(&sm[buf][tile]);
@@ -762,7 +752,7 @@ __device__ __forceinline__ void wgrad_tn_dma_body(const WgP& p, const int bx, co
   if constexpr (ABL != 3) issue(kbeg, 0);
   for (int ks = 0; ks < nk; ++ks) {
     const int cur = ks & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's share of buffer `cur` has landed
+    wait_vmcnt<0>();      // this wave's share of buffer `cur` has landed
     __builtin_amdgcn_s_barrier();                           // everybody's has, and everybody is past the MFMAs that read `cur ^ 1`
     const bool more = ks + 1 < nk;
     if (more && !SPREAD && ABL != 3) issue(kbeg + (ks + 1) * BK, cur ^ 1);
@@ -898,7 +888,7 @@ static int make_wgp(const jg_wgrad_args* a, WgP& p) {
   p.lddy = a->lddy; p.ldx = a->ldx; p.lddw = a->lddw;
   p.nh = a->nh; p.splitk = a->splitk;
   // JG_DETERMINISTIC 1: no split over the pixels -- every element of dw (and of dbias) is then produced by ONE thread of ONE workgroup, its
-  // atomicAdd a single add onto a reproducible value (the halo-resident kernels choose their own split: pick_split there)
+  // atomicAdd a single add onto a reproducible value (the halo-resident kernels choose their own split: jg_wgrad_pick_split)
   if (jg_tune(JG_TUNE_DETERMINISTIC) != 0 && a->out_mode == JG_OUT_ATOMIC_F32) p.splitk = 1;
   p.sdyb = a->sdyb; p.sdyh = a->sdyh; p.sxb = a->sxb; p.sxh = a->sxh; p.sdwb = a->sdwb; p.sdwh = a->sdwh;
   p.alpha = a->alpha; p.out_mode = a->out_mode; p.B = a->B;

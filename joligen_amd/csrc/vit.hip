@@ -15,9 +15,6 @@
 
 namespace {
 
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
-
 constexpr int BT = 64;       // rows per block / per streamed chunk
 
 // [row][32] 16-bit tiles in LDS (64-byte rows = 4 chunks of 16 B): chunk XOR for the ds_read_b128 operand fetch, 32-byte-block XOR

@@ -22,33 +22,10 @@
 #include "conv_params.h"
 #include "wgrad_params.h"
 #include "mfma_pipe.h"
+#include "lds_dma.h"      // glds16 / wait_vmcnt, tr_frag, the f2 / f4 / f8 / fdy swizzles, xcd_block_id
 #include <cstdlib>
 
 namespace {
-
-__device__ uint4 jg_wg_zero_page = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
-
-// 2-bit swizzle of a 128-byte pixel row (4 blocks of 32 B), by pixel column c
-__device__ __forceinline__ int f4(int c) { return ((c >> 1) & 1) | (((c >> 3) & 1) << 1); }
-// 3-bit swizzle of a 256-byte pixel row (8 blocks of 32 B)
-__device__ __forceinline__ int f8(int c) { return (c & 3) | (((c >> 3) & 1) << 2); }
-// 1-bit swizzle of a 64-byte pixel row (2 blocks of 32 B): the 8 pixels {h..h+3, h+8..h+11} of a service group are four bank quarters
-// (pixel % 4) x the two blocks, told apart by bit 3 of the column
-__device__ __forceinline__ int f2(int c) { return (c >> 3) & 1; }
-// block swizzle of a dy pixel row of BCO channels
-template <int BCO> __device__ __forceinline__ int fdy(int c) { return BCO == 32 ? f2(c) : BCO == 64 ? f4(c) : f8(c); }
 
 // XMODE 0: plain zero padding; 1: mirrored borders (REFLECT); 2: x is the half-resolution tensor read through the nearest-upsample map
 //
@@ -84,12 +61,7 @@ __global__ __launch_bounds__(WMR * 256, 3 - WMR) void wgrad3x3_halo_kernel(WgP p
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;   // wm < WMR
 
-  int id;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    id = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
-  }
+  const int id = xcd_block_id();
   const int pair = id % npairs, slice = id / npairs;
   const int co0 = (pair % ncot) * BCO, ci0 = (pair / ncot) * 64;
   const int t0 = slice * per;
@@ -98,7 +70,7 @@ __global__ __launch_bounds__(WMR * 256, 3 - WMR) void wgrad3x3_halo_kernel(WgP p
 
   const T* __restrict__ xg = (const T*)p.x + ci0;
   const T* __restrict__ dyg = (const T*)p.dy + co0;
-  const T* zp = reinterpret_cast<const T*>(&jg_wg_zero_page);
+  const T* zp = reinterpret_cast<const T*>(&jg_zero_page);
   typedef __attribute__((address_space(3))) char* lds_cptr;
   const unsigned lds0 = (unsigned)(size_t)(lds_cptr)(char*)&sm[0];
   const char* smb = reinterpret_cast<const char*>(&sm[0]);
@@ -221,11 +193,6 @@ __global__ __launch_bounds__(WMR * 256, 3 - WMR) void wgrad3x3_halo_kernel(WgP p
       bbase[s3][rd] = (trow * HW_ + hx) * 128 + ((wn ^ f4(hx)) << 5) + (i16 & 3) * 8;
     }
   }
-  auto tr_frag = [&](int off0, int off1) -> uint4 {
-    const uint2 u0 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off0)));
-    const uint2 u1 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off1)));
-    return make_uint4(u0.x, u0.y, u1.x, u1.y);
-  };
 
 #ifdef JG_WG_BLOAT
   asm volatile("" ::: "v255");     // experiment: the register footprint of the sliding-window kernel on this one
@@ -264,11 +231,11 @@ __global__ __launch_bounds__(WMR * 256, 3 - WMR) void wgrad3x3_halo_kernel(WgP p
       constexpr int NSTEP = NSUB * 9;
       auto load_fb = [&](int step) -> uint4 {
         const int sub = step / 9, t9 = step % 9, r = t9 / 3, s3 = t9 % 3;
-        return tr_frag(boff + bbase[s3][0] + (2 * sub + r) * (HW_ * 128), boff + bbase[s3][1] + (2 * sub + r) * (HW_ * 128));
+        return tr_frag(smb, boff + bbase[s3][0] + (2 * sub + r) * (HW_ * 128), boff + bbase[s3][1] + (2 * sub + r) * (HW_ * 128));
       };
       uint4 ring[LA + 1], fa[2][CPW];
 #pragma unroll
-      for (int i = 0; i < CPW; ++i) fa[0][i] = tr_frag(boff + abase[i][0], boff + abase[i][1]);
+      for (int i = 0; i < CPW; ++i) fa[0][i] = tr_frag(smb, boff + abase[i][0], boff + abase[i][1]);
 #pragma unroll
       for (int s = 0; s < LA; ++s) ring[s] = load_fb(s);
 #pragma unroll
@@ -278,7 +245,7 @@ __global__ __launch_bounds__(WMR * 256, 3 - WMR) void wgrad3x3_halo_kernel(WgP p
         if (t9 == 1 && sub + 1 < NSUB) {       // dy fragments of the next sub-step: 8 steps ahead of their first use
 #pragma unroll
           for (int i = 0; i < CPW; ++i)
-            fa[(sub + 1) & 1][i] = tr_frag(boff + abase[i][0] + (sub + 1) * 32 * DY_ROWB, boff + abase[i][1] + (sub + 1) * 32 * DY_ROWB);
+            fa[(sub + 1) & 1][i] = tr_frag(smb, boff + abase[i][0] + (sub + 1) * 32 * DY_ROWB, boff + abase[i][1] + (sub + 1) * 32 * DY_ROWB);
         }
         if (t9 == 0 && do_bias) {
 #pragma unroll
@@ -294,7 +261,7 @@ __global__ __launch_bounds__(WMR * 256, 3 - WMR) void wgrad3x3_halo_kernel(WgP p
       uint4 fa[CPW];
 #pragma unroll
       for (int i = 0; i < CPW; ++i)
-        fa[i] = tr_frag(boff + abase[i][0] + sub * 32 * DY_ROWB, boff + abase[i][1] + sub * 32 * DY_ROWB);
+        fa[i] = tr_frag(smb, boff + abase[i][0] + sub * 32 * DY_ROWB, boff + abase[i][1] + sub * 32 * DY_ROWB);
       if (do_bias) {
 #pragma unroll
         for (int i = 0; i < CPW; ++i) accb[i] = Mfma<T>::run(fa[i], ones, accb[i]);
@@ -302,7 +269,7 @@ __global__ __launch_bounds__(WMR * 256, 3 - WMR) void wgrad3x3_halo_kernel(WgP p
 #pragma unroll
       for (int t9 = 0; t9 < 9; ++t9) {
         const int r = t9 / 3, s3 = t9 % 3;
-        const uint4 fb = tr_frag(boff + bbase[s3][0] + (2 * sub + r) * (HW_ * 128), boff + bbase[s3][1] + (2 * sub + r) * (HW_ * 128));
+        const uint4 fb = tr_frag(smb, boff + bbase[s3][0] + (2 * sub + r) * (HW_ * 128), boff + bbase[s3][1] + (2 * sub + r) * (HW_ * 128));
 #pragma unroll
         for (int i = 0; i < CPW; ++i) acc[t9][i] = Mfma<T>::run(fa[i], fb, acc[t9][i]);
       }
@@ -376,12 +343,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_subpixel_kernel(WgP p, int nt
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
 
-  int id;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    id = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
-  }
+  const int id = xcd_block_id();
   const int pair = id % npairs, slice = id / npairs;
   const int co0 = (pair % ncot) * BCO, ci0 = (pair / ncot) * 64;
   const int t0 = slice * per;
@@ -390,7 +352,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_subpixel_kernel(WgP p, int nt
 
   const T* __restrict__ xg = (const T*)p.x + ci0;
   const T* __restrict__ dyg = (const T*)p.dy + co0;
-  const T* zp = reinterpret_cast<const T*>(&jg_wg_zero_page);
+  const T* zp = reinterpret_cast<const T*>(&jg_zero_page);
   typedef __attribute__((address_space(3))) char* lds_cptr;
   const unsigned lds0 = (unsigned)(size_t)(lds_cptr)(char*)&sm[0];
   const char* smb = reinterpret_cast<const char*>(&sm[0]);
@@ -470,11 +432,6 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_subpixel_kernel(WgP p, int nt
       bbase[s3][rd] = (trow * HW_ + hx) * 128 + ((wn ^ f4(hx)) << 5) + (i16 & 3) * 8;
     }
   }
-  auto tr_frag = [&](int off0, int off1) -> uint4 {
-    const uint2 u0 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off0)));
-    const uint2 u1 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off1)));
-    return make_uint4(u0.x, u0.y, u1.x, u1.y);
-  };
 
   // acc[((py * 2 + px) * 2 + a) * 2 + b]
   f32x4 acc[16][CPW], accb[CPW];
@@ -505,12 +462,12 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_subpixel_kernel(WgP p, int nt
       auto load_fb = [&](int step) -> uint4 {
         const int sub = step >> 4, ph = (step >> 2) & 3, a = (step >> 1) & 1, b = step & 1;
         const int row = 2 * sub + a + (ph >> 1), s3 = b + (ph & 1);
-        return tr_frag(bbase[s3][0] + row * (HW_ * 128), bbase[s3][1] + row * (HW_ * 128));
+        return tr_frag(smb, bbase[s3][0] + row * (HW_ * 128), bbase[s3][1] + row * (HW_ * 128));
       };
       auto load_fa = [&](int grp, uint4 (&fa)[CPW]) {      // grp = sub * 4 + ph
         const int off = ((grp & 3) * PL_CH * 16) + (grp >> 2) * 32 * DY_ROWB;
 #pragma unroll
-        for (int i = 0; i < CPW; ++i) fa[i] = tr_frag(abase[i][0] + off, abase[i][1] + off);
+        for (int i = 0; i < CPW; ++i) fa[i] = tr_frag(smb, abase[i][0] + off, abase[i][1] + off);
       };
       uint4 ring[LA + 1], fa[2][CPW];
       load_fa(0, fa[0]);
@@ -583,27 +540,6 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_subpixel_kernel(WgP p, int nt
   }
 }
 
-// Split-K choice: `slots` workgroups run at a time (1 or 2 per CU by LDS), so the launch runs in rounds; every block
-// walks `per` tiles and pays a fixed prologue + atomic epilogue worth about OVH tiles.
-static void pick_split(int npairs, int ntiles, int ovh, int slots, int* per_out, int* splitk_out) {
-  long best = -1;
-  int bper = ntiles, bsk = 1;
-  if (jg_tune(JG_TUNE_DETERMINISTIC) != 0) {     // no split over the tiles: one workgroup, one thread per element of dw -- a reproducible sum
-    *per_out = ntiles; *splitk_out = 1;
-    return;
-  }
-  const int skmax = ntiles < 2048 / npairs + 1 ? ntiles : 2048 / npairs + 1;
-  for (int sk = 1; sk <= skmax; ++sk) {
-    const int per = (ntiles + sk - 1) / sk;
-    const int ske = (ntiles + per - 1) / per;
-    const long blocks = (long)npairs * ske;
-    const long rounds = (blocks + slots - 1) / slots;
-    const long cost = (long)(per + ovh) * rounds;
-    if (best < 0 || cost < best) { best = cost; bper = per; bsk = ske; }
-  }
-  *per_out = bper; *splitk_out = bsk;
-}
-
 template <typename T, int TH, int CPW, int WMR, int XMODE = 0>
 void launch_wg(const WgP& p, hipStream_t st) {
   // JG_WGRAD_PIPE (1): the software-pipelined MFMA loop for the CPW == 2 tiles (the CPW == 4 tiles have no registers left for the ring)
@@ -612,7 +548,7 @@ void launch_wg(const WgP& p, hipStream_t st) {
   const int ncot = (p.Cout + BCO - 1) / BCO, npairs = ncot * (p.Cin / 64);
   const int ntiles = p.B * (p.H / TH) * (p.W >> 4);
   int per, splitk;
-  pick_split(npairs, ntiles, TH == 16 ? 6 : 10, WMR == 1 && jg_tune(JG_TUNE_WGRAD_LDS_PAD) < 4096 ? 512 : 256, &per, &splitk);
+  jg_wgrad_pick_split(npairs, ntiles, TH == 16 ? 6 : 10, WMR == 1 && jg_tune(JG_TUNE_WGRAD_LDS_PAD) < 4096 ? 512 : 256, &per, &splitk);
   // JG_WGRAD_LDS_PAD: extra (unused) dynamic LDS bytes, an occupancy lever for A/B runs: e.g. the 4-wave configuration at one workgroup per
   // CU instead of two leaves half of every SIMD's register file to the kernels of the other stream
   const size_t pad = (size_t)jg_tune(JG_TUNE_WGRAD_LDS_PAD);
@@ -628,7 +564,7 @@ void launch_subpixel(const WgP& p, hipStream_t st) {
   const int ntiles = p.B * ((p.H >> 1) / TL) * (p.W >> 5);
   int per, splitk;
   // a tile is 64 MFMAs per wave (144 in the 16-row tile, whose prologue + atomic epilogue are worth 6 of its tiles)
-  pick_split(npairs, ntiles, 14, 256, &per, &splitk);
+  jg_wgrad_pick_split(npairs, ntiles, 14, 256, &per, &splitk);
   jg_note_kernel("wgrad3x3_halo_kernel<subpixel,4 rows,64 co>");
   hipLaunchKernelGGL((wgrad3x3_subpixel_kernel<T, TL, 3>), dim3(npairs * splitk), dim3(512), 0, st, p, ntiles, per, npairs, ncot);
 }

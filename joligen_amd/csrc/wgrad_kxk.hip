@@ -11,27 +11,12 @@
 // tiles per co-block for 7x7 with RT = 2), and walks over a slice of TH x 16 spatial tiles (split over tiles, fp32 atomics at the end).
 // Per tile the dy tile [TH*16 px][32] and the x halo [(TH+RT-1) x (16+KS-1) px][64] come into LDS once (LDS-DMA, double buffered) and all
 // RT x KS taps read the halo at shifted positions: the input is fetched ceil(KS / RT) x 1.5 times instead of KS^2 / 2 times.
-// LDS images, swizzles and the transposing fragment reads (ds_read_b64_tr_b16) are those of wgrad_halo.hip.
+// LDS images are those of wgrad_halo.hip; the LDS-DMA, the f2 / f4 swizzles (dy rows of 64 bytes, halo rows of 128) and the transposing
+// fragment reads (ds_read_b64_tr_b16) are the shared ones of lds_dma.h.
 #include "wgrad_params.h"
+#include "lds_dma.h"
 
 namespace {
-
-__device__ uint4 jg_wk_zero_page = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
-
-// 2-bit swizzle of a 128-byte halo pixel row (4 blocks of 32 B) by pixel column (wgrad_halo.hip)
-__device__ __forceinline__ int f4(int c) { return ((c >> 1) & 1) | (((c >> 3) & 1) << 1); }
-// 1-bit swizzle of a 64-byte dy pixel row (2 blocks of 32 B): a 32-lane service group reads pixels {h..h+3, h+8..h+11}
-__device__ __forceinline__ int f2(int c) { return (c >> 3) & 1; }
 
 template <typename T, int KS, int RT, int TH, int CPW>
 __global__ __launch_bounds__(256, 2) void wgrad_kxk_halo_kernel(WgP p, int ntiles, int per, int npairs, int ncot, int ngroups) {
@@ -63,7 +48,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kxk_halo_kernel(WgP p, int ntile
 
   const T* __restrict__ xg = (const T*)p.x + ci0;
   const T* __restrict__ dyg = (const T*)p.dy + co0;
-  const T* zp = reinterpret_cast<const T*>(&jg_wk_zero_page);
+  const T* zp = reinterpret_cast<const T*>(&jg_zero_page);
   typedef __attribute__((address_space(3))) char* lds_cptr;
   const unsigned lds0 = (unsigned)(size_t)(lds_cptr)(char*)&sm[0];
   const char* smb = reinterpret_cast<const char*>(&sm[0]);
@@ -115,11 +100,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kxk_halo_kernel(WgP p, int ntile
       bbase[s][rd] = (trow * HW_ + hx) * 128 + ((wave ^ f4(hx)) << 5) + (i16 & 3) * 8;
     }
   }
-  auto tr_frag = [&](int off0, int off1) -> uint4 {
-    const uint2 u0 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off0)));
-    const uint2 u1 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off1)));
-    return make_uint4(u0.x, u0.y, u1.x, u1.y);
-  };
 
   f32x4 acc[RT * KS][CPW], accb[CPW];
 #pragma unroll
@@ -149,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kxk_halo_kernel(WgP p, int ntile
     for (int sub = 0; sub < NSUB; ++sub) {
       uint4 fa[CPW];
 #pragma unroll
-      for (int i = 0; i < CPW; ++i) fa[i] = tr_frag(boff + abase[i][0] + sub * 32 * DY_ROWB, boff + abase[i][1] + sub * 32 * DY_ROWB);
+      for (int i = 0; i < CPW; ++i) fa[i] = tr_frag(smb, boff + abase[i][0] + sub * 32 * DY_ROWB, boff + abase[i][1] + sub * 32 * DY_ROWB);
       if (do_bias) {
 #pragma unroll
         for (int i = 0; i < CPW; ++i) accb[i] = Mfma<T>::run(fa[i], ones, accb[i]);
@@ -158,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kxk_halo_kernel(WgP p, int ntile
       for (int r = 0; r < RT; ++r)
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-          const uint4 fb = tr_frag(boff + bbase[s][0] + (2 * sub + r) * (HW_ * 128), boff + bbase[s][1] + (2 * sub + r) * (HW_ * 128));
+          const uint4 fb = tr_frag(smb, boff + bbase[s][0] + (2 * sub + r) * (HW_ * 128), boff + bbase[s][1] + (2 * sub + r) * (HW_ * 128));
 #pragma unroll
           for (int i = 0; i < CPW; ++i) acc[r * KS + s][i] = Mfma<T>::run(fa[i], fb, acc[r * KS + s][i]);
         }

@@ -16,32 +16,20 @@
 // The 8 waves of a workgroup are 2 row halves x 2 co blocks x 2 ci blocks; the two row halves of a block are summed through LDS (the
 // tile buffers are free by then) so that the atomic volume is that of the kernel it replaces.
 //
-// LDS images, LDS-DMA issue, tile walk, split-K policy and the XMODE forms (mirrored borders, upsample-on-read) are those of
-// wgrad_halo.hip; the swizzle differs because a 32-lane service group of the transposing read now covers 4 pixels x 64 B (two 32-byte
-// channel blocks of one pixel side by side): the 64-byte block index of a 128-byte pixel row is XORed with bit 1 of the pixel column,
-// which with the parity of the column (the pixel stride is 128 B = half a bank row) spreads any four consecutive columns over the four
-// 64-byte bank quarters -- for every tap shift.
+// LDS images, tile walk and the XMODE forms (mirrored borders, upsample-on-read) are those of wgrad_halo.hip, the LDS-DMA and fragment
+// helpers those of lds_dma.h, the split-K policy that of wgrad_params.h; the swizzle differs because a 32-lane service group of the
+// transposing read now covers 4 pixels x 64 B (two 32-byte channel blocks of one pixel side by side): the 64-byte block index of a
+// 128-byte pixel row is XORed with bit 1 of the pixel column, which with the parity of the column (the pixel stride is 128 B = half a
+// bank row) spreads any four consecutive columns over the four 64-byte bank quarters -- for every tap shift.
 #include "conv_params.h"
 #include "wgrad_params.h"
+#include "lds_dma.h"
 #include <type_traits>
 
 namespace {
 
-__device__ uint4 jg_sw_zero_page = {0u, 0u, 0u, 0u};
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // ONE v_mfma_f32_32x32x16 as a pinned statement (mfma_pipe.h::jg_mfma_pinned for the 32x32 shape): the compiler keeps the source order
 // of the transposing LDS reads and the MFMAs and still counts lgkmcnt for the reads (they stay builtins)
@@ -92,12 +80,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_sw_kernel(WgP p, int ntiles, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;    // row half, 32-co block, 32-ci block
 
-  int id;
-  {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    id = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
-  }
+  const int id = xcd_block_id();
   const int pair = id % npairs, slice = id / npairs;
   const int co0 = (pair % ncot) * BCO, ci0 = (pair / ncot) * 64;
   const int t0 = slice * per;
@@ -106,7 +89,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_sw_kernel(WgP p, int ntiles, 
 
   const T* __restrict__ xg = (const T*)p.x + ci0;
   const T* __restrict__ dyg = (const T*)p.dy + co0;
-  const T* zp = reinterpret_cast<const T*>(&jg_sw_zero_page);
+  const T* zp = reinterpret_cast<const T*>(&jg_zero_page);
   typedef __attribute__((address_space(3))) char* lds_cptr;
   const unsigned lds0 = (unsigned)(size_t)(lds_cptr)(char*)&sm[0];
   const char* smb = reinterpret_cast<const char*>(&sm[0]);
@@ -193,11 +176,6 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_sw_kernel(WgP p, int ntiles, 
       bbase[s3][rd] = (wr * 8 * HW_ + hx) * 128 + (((wn ^ fx(hx)) << 6) | ((j & 1) << 5)) + (i16 & 3) * 8;
     }
   }
-  auto tr_frag = [&](int off0, int off1) -> uint4 {
-    const uint2 u0 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off0)));
-    const uint2 u1 = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(smb + off1)));
-    return make_uint4(u0.x, u0.y, u1.x, u1.y);
-  };
 
   f32x16 acc[9];
 #pragma unroll
@@ -230,11 +208,11 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_sw_kernel(WgP p, int ntiles, 
     // column, a whole step (9 MFMAs) ahead of its next use; the dy rows sit in a ring of four, row hl + 1 requested at the top of step hl.
     uint4 xf[3], dyf[4];
 #pragma unroll
-    for (int s3 = 0; s3 < 3; ++s3) xf[s3] = tr_frag(boff + bbase[s3][0], boff + bbase[s3][1]);
-    dyf[0] = tr_frag(boff + abase[0], boff + abase[1]);
+    for (int s3 = 0; s3 < 3; ++s3) xf[s3] = tr_frag(smb, boff + bbase[s3][0], boff + bbase[s3][1]);
+    dyf[0] = tr_frag(smb, boff + abase[0], boff + abase[1]);
 #pragma unroll
     for (int hl = 0; hl < RH + 2; ++hl) {
-      if (hl + 1 < RH) dyf[(hl + 1) & 3] = tr_frag(boff + abase[0] + (hl + 1) * DROW, boff + abase[1] + (hl + 1) * DROW);
+      if (hl + 1 < RH) dyf[(hl + 1) & 3] = tr_frag(smb, boff + abase[0] + (hl + 1) * DROW, boff + abase[1] + (hl + 1) * DROW);
       if (hl < RH && do_bias) bsum += sum8<T>(dyf[hl & 3]);
 #pragma unroll
       for (int s3 = 0; s3 < 3; ++s3) {
@@ -243,7 +221,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_sw_kernel(WgP p, int ntiles, 
           const int y = hl - r;
           if (y >= 0 && y < RH) mfma32_pinned<T>(acc[r * 3 + s3], dyf[y & 3], xf[s3]);
         }
-        if (hl + 1 < RH + 2) xf[s3] = tr_frag(boff + bbase[s3][0] + (hl + 1) * HROW, boff + bbase[s3][1] + (hl + 1) * HROW);
+        if (hl + 1 < RH + 2) xf[s3] = tr_frag(smb, boff + bbase[s3][0] + (hl + 1) * HROW, boff + bbase[s3][1] + (hl + 1) * HROW);
       }
     }
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");     // the compiler does not see the MFMAs: keep its next VALU access off their results
@@ -296,32 +274,12 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_sw_kernel(WgP p, int ntiles, 
   }
 }
 
-// Split-K choice of wgrad_halo.hip: one workgroup per CU, a block walks `per` tiles and pays a fixed prologue + epilogue of about OVH tiles
-static void pick_split(int npairs, int ntiles, int ovh, int slots, int* per_out, int* splitk_out) {
-  long best = -1;
-  int bper = ntiles, bsk = 1;
-  if (jg_tune(JG_TUNE_DETERMINISTIC) != 0) {     // no split over the tiles: one workgroup, one thread per element of dw -- a reproducible sum
-    *per_out = ntiles; *splitk_out = 1;
-    return;
-  }
-  const int skmax = ntiles < 2048 / npairs + 1 ? ntiles : 2048 / npairs + 1;
-  for (int sk = 1; sk <= skmax; ++sk) {
-    const int per = (ntiles + sk - 1) / sk;
-    const int ske = (ntiles + per - 1) / per;
-    const long blocks = (long)npairs * ske;
-    const long rounds = (blocks + slots - 1) / slots;
-    const long cost = (long)(per + ovh) * rounds;
-    if (best < 0 || cost < best) { best = cost; bper = per; bsk = ske; }
-  }
-  *per_out = bper; *splitk_out = bsk;
-}
-
 template <typename T, int XMODE>
 void launch_sw(const WgP& p, hipStream_t st) {
   const int ncot = (p.Cout + 63) / 64, npairs = ncot * (p.Cin / 64);
   const int ntiles = p.B * (p.H / 16) * (p.W >> 4);
   int per, splitk;
-  pick_split(npairs, ntiles, 6, 256, &per, &splitk);
+  jg_wgrad_pick_split(npairs, ntiles, 6, 256, &per, &splitk);      // one workgroup per CU; prologue + epilogue are worth about 6 tiles
   hipLaunchKernelGGL((wgrad3x3_sw_kernel<T, XMODE>), dim3(npairs * splitk), dim3(512), 0, st, p, ntiles, per, npairs, ncot, jg_tune(JG_TUNE_HALO_DBG));
 }
 

@@ -42,7 +42,7 @@ def rnd(shape, dtype, seed, scale=1.0):
 
 
 def pick_split(npairs, ntiles, ovh=14, slots=256):
-    """csrc/wgrad_halo.hip pick_split with launch_subpixel's arguments: (tiles per slice, slices)"""
+    """csrc/wgrad_params.h jg_wgrad_pick_split with wgrad_halo.hip launch_subpixel's arguments: (tiles per slice, slices)"""
     best, bper, bsk = -1, ntiles, 1
     for sk in range(1, min(ntiles, 2048 // npairs + 1) + 1):
         per = (ntiles + sk - 1) // sk

@@ -65,7 +65,7 @@ def test_tables_reproduce_autograd_in_float64():
             assert torch.allclose(got, w.grad[:, :, r, s], rtol=1e-12, atol=1e-12), (r, s)
 
 
-def f4(c):
+def f4(c):      # csrc/lds_dma.h f4: 2-bit block swizzle of a 128-byte pixel row by pixel column
     return ((c >> 1) & 1) | (((c >> 3) & 1) << 1)
 
 

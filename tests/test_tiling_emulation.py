@@ -3,7 +3,9 @@ csrc/gemm_tn.hip): who stages which 16-byte chunk into which (swizzled) LDS slot
 lane reads as its MFMA fragment, and where each accumulator register is stored.  The MFMA itself
 is modelled with the documented gfx950 layout of v_mfma_f32_16x16x32_{f16,bf16}
 (cdna_hip_programming.md section 3): operand lane l holds row/col (l & 15), k-group (l >> 4), 8
-consecutive k; D[row = (l >> 4) * 4 + reg][col = l & 15].
+consecutive k; D[row = (l >> 4) * 4 + reg][col = l & 15].  (The helpers those kernels share with the
+halo-resident ones -- LDS-DMA issue, zero page, XCD tile order, the transposing fragment read -- are in
+csrc/lds_dma.h; the swizzles emulated here, swz64 / swz128 / swz_tr, are the two files' own.)
 
 This is host-logic test infrastructure (no GPU): it transcribes the kernels' integer arithmetic
 line by line so that a layout mistake is caught before burning GPU minutes; it also checks the LDS
