@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .._autograd import JGFunction
-from .. import _lib, ops
+from .. import _lib, launch, ops
 from .._lib import check
 from ..ops import JG_ACT_LRELU, _dt, _p, _st, conv_nt, wgrad_tn
 from .layers import JGConv2d, JGConvNd
@@ -39,22 +39,13 @@ class _Bilinear2Fn(JGFunction):
 
     @staticmethod
     def forward(ctx, x, Ho, Wo, align):
-        x = x.contiguous()
-        B, H, W, C = x.shape
-        y = torch.empty((B, Ho, Wo, C), device=x.device, dtype=x.dtype)
-        check(_lib.lib().jg_bilinear2_fwd(_dt(x), x.data_ptr(), y.data_ptr(), B, H, W, C, Ho, Wo, C, int(align), _st()), "jg_bilinear2_fwd")
-        ctx.geo = (H, W, Ho, Wo, int(align))
-        return y
+        ctx.geo = (x.shape[1], x.shape[2], align)
+        return launch.bilinear2_fwd(x.contiguous(), Ho, Wo, align)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        H, W, Ho, Wo, align = ctx.geo
-        dy = dy.contiguous()
-        B, C = dy.shape[0], dy.shape[-1]
-        dx = torch.empty((B, H, W, C), device=dy.device, dtype=dy.dtype)
-        check(_lib.lib().jg_bilinear2_bwd(_dt(dy), dy.data_ptr(), dx.data_ptr(), B, H, W, C, Ho, Wo, C, align, _st()), "jg_bilinear2_bwd")
-        return dx, None, None, None
+        return launch.bilinear2_bwd(dy.contiguous(), *ctx.geo), None, None, None
 
 
 def bilinear(x, Ho, Wo, align_corners):
@@ -74,12 +65,7 @@ class _AddFn(JGFunction):
 class _HingeFn(JGFunction):
     @staticmethod
     def forward(ctx, pred, mode, scale):
-        pred = pred.contiguous()
-        loss = torch.zeros((), device=pred.device, dtype=torch.float32)
-        dpred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
-        check(_lib.lib().jg_hinge_loss(_dt(pred), pred.data_ptr(), loss.data_ptr(), _p(dpred), pred.numel(), 1, 1, mode, scale, 1.0, _st()),
-              "jg_hinge_loss")
-        ctx.dpred = dpred
+        loss, ctx.dpred = launch.hinge_loss(pred.contiguous(), mode, scale, ctx.needs_input_grad[0])
         return loss
 
     @staticmethod
@@ -212,7 +198,6 @@ class _SpectralConvFn(JGFunction):
         B, H, W_, Cin = x.shape
         assert Cin == m.Cin, (Cin, m.Cin)
         dev = x.device
-        K = m.R * m.S * m.Cin_real
         prepared = getattr(mod, "_sn_pass", None)
         if prepared is not None:               # this layer's power iteration and working copies were made with all the others'
             mod._sn_pass = None
@@ -229,9 +214,7 @@ class _SpectralConvFn(JGFunction):
         sigma = torch.empty(1, device=dev, dtype=torch.float32)
         Wp = weight_orig.data_ptr()            # arena slice: physical [Cout][R][S][Cin] fp32
         if mod.training:
-            ws = torch.empty(K + m.Cout_real + 2, device=dev, dtype=torch.float32)
-            check(L.jg_spectral_power_iter(Wp, mod.weight_u.data_ptr(), mod.weight_v.data_ptr(), sigma.data_ptr(), ws.data_ptr(), m.Cout_real,
-                                           m.R * m.S, m.Cin_real, 1e-12, _st()), "jg_spectral_power_iter")
+            launch.spectral_power_iter(weight_orig, mod.weight_u, mod.weight_v, sigma, m.Cout_real, m.R * m.S, m.Cin_real)
         else:       # eval: sigma from the stored vectors (torch.nn.utils.spectral_norm does not iterate in eval mode)
             Wl = weight_orig.detach().reshape(m.Cout_real, -1)
             sigma.copy_(torch.dot(mod.weight_u, Wl @ mod.weight_v).reshape(1))
@@ -257,7 +240,6 @@ class _SpectralConvFn(JGFunction):
             x, w16T, sigma, u, v = ctx.saved_tensors
         mod = ctx.mod
         m = mod.meta
-        L = _lib.lib()
         dy = dy.contiguous()
         B, H, W_, Cin = x.shape
         _, Ho, Wo, Cout = dy.shape
@@ -286,9 +268,7 @@ class _SpectralConvFn(JGFunction):
             if ctx.sn is not None:             # the sigma-gradient fix of all layers runs once, when the last one has delivered its dWsn
                 ctx.sn[0].delivered(ctx.sn[1])
                 return dx, None, None, None
-            ws = torch.empty(1, device=dy.device, dtype=torch.float32)
-            check(L.jg_spectral_wgrad_fix(dwsn.data_ptr(), mod.weight_orig.data_ptr(), u.data_ptr(), v.data_ptr(), sigma.data_ptr(), wg.data_ptr(),
-                                          ws.data_ptr(), m.Cout_real, m.R * m.S, m.Cin_real, _st()), "jg_spectral_wgrad_fix")
+            launch.spectral_wgrad_fix(dwsn, mod.weight_orig, u, v, sigma, wg, m.Cout_real, m.R * m.S, m.Cin_real)
         return dx, None, None, None
 
 

@@ -25,8 +25,9 @@ import torch
 import torch.nn as nn
 
 from .._autograd import JGFunction
-from .. import _lib, ops
+from .. import _lib, launch, ops
 from .._lib import check
+from ..launch import vit_attention_bwd, vit_attention_fwd
 from ..ops import JG_ACT_RELU, _dt, _gemm_geom, _p, _st, conv_nt
 from .layers import JGConv1d, JGConv2d, JGLinear
 from .projected_d import _AddFn
@@ -103,13 +104,7 @@ def _lin_dgrad(dy, m):
 
 
 def _ln_fwd(x, ln, want_stats):
-    y = torch.empty_like(x)
-    C = x.shape[-1]
-    R = x.numel() // C
-    mr = torch.empty((R, 2), device=x.device, dtype=torch.float32) if want_stats else None
-    check(_lib.lib().jg_layernorm_fwd(_dt(x), x.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), y.data_ptr(), _p(mr), R, C, ln.eps, _st()),
-          "jg_layernorm_fwd")
-    return y, mr
+    return launch.layernorm_fwd(x, ln.weight, ln.bias, ln.eps, want_stats)
 
 
 def _ln_bwd_res(x, dy, ln, mr, res):
@@ -118,32 +113,6 @@ def _ln_bwd_res(x, dy, ln, mr, res):
     check(_lib.lib().jg_layernorm_bwd_res(_dt(x), x.data_ptr(), dy.data_ptr(), ln.weight.data_ptr(), mr.data_ptr(), _p(res), dx.data_ptr(),
                                           x.numel() // C, C, _st()), "jg_layernorm_bwd_res")
     return dx
-
-
-def vit_attention_fwd(qkv, heads):
-    """timm Attention core on the packed projection qkv [B, T, 3C] (channel order [3][heads][head_dim]) -> (a [B, T, C], logsumexp)"""
-    B, T, C3 = qkv.shape
-    C = C3 // 3
-    hd = C // heads
-    a = torch.empty((B, T, C), device=qkv.device, dtype=qkv.dtype)
-    L = torch.empty((B * heads, T), device=qkv.device, dtype=torch.float32)
-    es = qkv.element_size()
-    check(_lib.lib().jg_vit_attention_fwd(_dt(qkv), qkv.data_ptr(), qkv.data_ptr() + C * es, qkv.data_ptr() + 2 * C * es, C3, hd, a.data_ptr(),
-                                          L.data_ptr(), B, T, heads, hd, hd ** -0.5, _st()), "jg_vit_attention_fwd")
-    return a, L
-
-
-def vit_attention_bwd(qkv, a, L, da, heads):
-    B, T, C3 = qkv.shape
-    C = C3 // 3
-    hd = C // heads
-    dqkv = torch.empty_like(qkv)
-    Dq = torch.empty((B * heads, T), device=qkv.device, dtype=torch.float32)
-    es = qkv.element_size()
-    check(_lib.lib().jg_vit_attention_bwd(_dt(qkv), qkv.data_ptr(), qkv.data_ptr() + C * es, qkv.data_ptr() + 2 * C * es, C3, hd, a.data_ptr(),
-                                          L.data_ptr(), da.data_ptr(), dqkv.data_ptr(), dqkv.data_ptr() + C * es, dqkv.data_ptr() + 2 * C * es, C3,
-                                          Dq.data_ptr(), B, T, heads, hd, hd ** -0.5, _st()), "jg_vit_attention_bwd")
-    return dqkv
 
 
 class _VitAttnFn(JGFunction):
@@ -166,18 +135,6 @@ class _VitAttnFn(JGFunction):
 
 def vit_attention(qkv, heads):
     return _VitAttnFn.apply(qkv, heads)
-
-
-def _gelu(x):
-    y = torch.empty_like(x)
-    check(_lib.lib().jg_gelu_fwd(_dt(x), x.data_ptr(), y.data_ptr(), x.numel(), _st()), "jg_gelu_fwd")
-    return y
-
-
-def _gelu_bwd(x, dy):
-    dx = torch.empty_like(x)
-    check(_lib.lib().jg_gelu_bwd(_dt(x), x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), _st()), "jg_gelu_bwd")
-    return dx
 
 
 class _VitTokensFn(JGFunction):
@@ -208,7 +165,7 @@ class _VitTokensFn(JGFunction):
             t2 = _lin(a, blk.attn.proj.meta, res=t)
             h2, mr2 = _ln_fwd(t2, blk.norm2, keep)
             u = _lin(h2, blk.mlp.fc1.meta)
-            t3 = _lin(_gelu(u), blk.mlp.fc2.meta, res=t2)
+            t3 = _lin(launch.gelu_fwd(u), blk.mlp.fc2.meta, res=t2)
             if keep:
                 saved.append((t, mr1, qkv, a, lse, t2, mr2, u))
             t = t3
@@ -236,7 +193,7 @@ class _VitTokensFn(JGFunction):
             t, mr1, qkv, a, lse, t2, mr2, u = saved[i]
             saved[i] = None
             dg = _lin_dgrad(dt, blk.mlp.fc2.meta)
-            du = _gelu_bwd(u, dg)
+            du = launch.gelu_bwd(u, dg)
             dh2 = _lin_dgrad(du, blk.mlp.fc1.meta)
             dt2 = _ln_bwd_res(t2, dh2, blk.norm2, mr2, dt)               # dt2 = dt + LN2'(dh2)
             da = _lin_dgrad(dt2, blk.attn.proj.meta)

@@ -25,30 +25,8 @@ from ._autograd import JGFunction
 from . import _lib
 from ._lib import (JG_ACT_LRELU, JG_ACT_NONE, JG_ACT_RELU, JG_ACT_SILU, JG_ACT_TANH, JG_OUT_ATOMIC_F32, JG_OUT_STORE_T, ConvArgs,
                    WgradArgs, check)
-
-_DT = {torch.float16: _lib.JG_F16, torch.bfloat16: _lib.JG_BF16}
-
-
-def _dt(t: torch.Tensor) -> int:
-    try:
-        return _DT[t.dtype]
-    except KeyError:
-        raise TypeError(f"joligen_amd activations must be float16/bfloat16, got {t.dtype}") from None
-
-
-# torch.cuda.current_stream() builds a Stream object per call (~8 us): too slow for a per-launch lookup.  The raw accessor is a private
-# symbol: a torch build without it (or without CUDA / HIP at all) falls back to the public API instead of failing at import time
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda dev: torch.cuda.current_stream(dev).cuda_stream)
-_cur_device = torch.cuda.current_device
-
-
-def _st() -> int:
-    """raw hipStream_t of torch's current stream on the current device"""
-    return _raw_stream(_cur_device())
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
+from . import launch
+from .launch import SINKHORN_ITERS, _DT, _dt, _p, _raw_stream, _st, sgemm  # noqa: F401  (plumbing, re-exported under its old names)
 
 
 def _require_cuda(*ts):
@@ -639,9 +617,7 @@ class _ReflectConv2dFn(JGFunction):
                 check(_lib.lib().jg_reflect_dgrad_border(_dt(dy), dy.data_ptr(), m.Cout, m.w16T.data_ptr(), dx.data_ptr(), Cin, ws.data_ptr(), B, H, W,
                                                          m.Cout, Cin, 1.0, _st()), "jg_reflect_dgrad_border")
             else:
-                dxp = conv2d_dgrad(dy, m, (B, H + 2, W + 2, Cin))
-                dx = torch.empty_like(x)
-                check(_lib.lib().jg_reflect_pad2d_bwd(_dt(dy), dxp.data_ptr(), dx.data_ptr(), B, H, W, Cin, 1, _st()), "jg_reflect_pad2d_bwd")
+                dx = launch.reflect_pad2d_bwd(conv2d_dgrad(dy, m, (B, H + 2, W + 2, Cin)), 1)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             wg = m.weight.grad
             if wg is None:
@@ -713,28 +689,34 @@ def zeros_f32(n, device):
     return out
 
 
+def _group_norm_launch(x, gamma, beta, film, G, act, eps, sums=None, add=None):
+    """the GroupNorm forward chain: statistics (unless given), coefficients, apply (+ add) -> (y, ab [B, C, 2], mr [B, G, 2])"""
+    _require_cuda(x)
+    L = _lib.lib()
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    dev, st, dt = x.device, _st(), _dt(x)
+    ab = torch.empty((B, C, 2), device=dev, dtype=torch.float32)
+    mr = torch.empty((B, G, 2), device=dev, dtype=torch.float32)
+    y = torch.empty_like(x)
+    ldfilm = film.stride(0) if film is not None else 0
+    if sums is None:            # (given: the producing convolution's epilogue has accumulated them, ops.conv2d_stats)
+        sums = zeros_f32(B * C * 2, dev)[:B * C * 2].view(B, C, 2)
+        check(L.jg_gn_stats_ld(dt, x.data_ptr(), C, sums.data_ptr(), C, B, HW, C, st), "jg_gn_stats_ld")
+    check(L.jg_gn_coef(sums.data_ptr(), _p(gamma), _p(beta), _p(film), ldfilm, ab.data_ptr(), mr.data_ptr(), B, HW, C,
+                       G, eps, st), "jg_gn_coef")
+    if add is not None:          # y = act(norm(x)) + add in the apply pass (round 6); d(add) = dy
+        add = add.contiguous()
+        check(L.jg_gn_apply_add(dt, x.data_ptr(), C, ab.data_ptr(), add.data_ptr(), C, y.data_ptr(), C, B, HW, C, act, st), "jg_gn_apply_add")
+    else:
+        check(L.jg_gn_apply(dt, x.data_ptr(), ab.data_ptr(), y.data_ptr(), B, HW, C, act, st), "jg_gn_apply")
+    return y, ab, mr
+
+
 class _GroupNormFn(JGFunction):
     @staticmethod
     def forward(ctx, x, gamma, beta, film, G, act, eps, sums=None, add=None):
-        _require_cuda(x)
-        L = _lib.lib()
-        B, C = x.shape[0], x.shape[-1]
-        HW = x.numel() // (B * C)
-        dev, st, dt = x.device, _st(), _dt(x)
-        ab = torch.empty((B, C, 2), device=dev, dtype=torch.float32)
-        mr = torch.empty((B, G, 2), device=dev, dtype=torch.float32)
-        y = torch.empty_like(x)
-        ldfilm = film.stride(0) if film is not None else 0
-        if sums is None:            # (given: the producing convolution's epilogue has accumulated them, ops.conv2d_stats)
-            sums = zeros_f32(B * C * 2, dev)[:B * C * 2].view(B, C, 2)
-            check(L.jg_gn_stats_ld(dt, x.data_ptr(), C, sums.data_ptr(), C, B, HW, C, st), "jg_gn_stats_ld")
-        check(L.jg_gn_coef(sums.data_ptr(), _p(gamma), _p(beta), _p(film), ldfilm, ab.data_ptr(), mr.data_ptr(), B, HW, C,
-                           G, eps, st), "jg_gn_coef")
-        if add is not None:          # y = act(norm(x)) + add in the apply pass (round 6); d(add) = dy
-            add = add.contiguous()
-            check(L.jg_gn_apply_add(dt, x.data_ptr(), C, ab.data_ptr(), add.data_ptr(), C, y.data_ptr(), C, B, HW, C, act, st), "jg_gn_apply_add")
-        else:
-            check(L.jg_gn_apply(dt, x.data_ptr(), ab.data_ptr(), y.data_ptr(), B, HW, C, act, st), "jg_gn_apply")
+        y, ab, mr = _group_norm_launch(x, gamma, beta, film, G, act, eps, sums, add)
         ctx.save_for_backward(x, ab, mr, gamma, beta, film)
         ctx.G, ctx.act = G, act
         return y
@@ -866,20 +848,13 @@ class _ReflectPadFn(JGFunction):
     @staticmethod
     def forward(ctx, x, pad):
         _require_cuda(x)
-        B, H, W, Cc = x.shape
-        y = torch.empty((B, H + 2 * pad, W + 2 * pad, Cc), device=x.device, dtype=x.dtype)
-        check(_lib.lib().jg_reflect_pad2d(_dt(x), x.contiguous().data_ptr(), y.data_ptr(), B, H, W, Cc, pad, _st()), "jg_reflect_pad2d")
-        ctx.pad, ctx.shape = pad, x.shape
-        return y
+        ctx.pad = pad
+        return launch.reflect_pad2d(x.contiguous(), pad)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        B, H, W, Cc = ctx.shape
-        dx = torch.empty(ctx.shape, device=dy.device, dtype=dy.dtype)
-        check(_lib.lib().jg_reflect_pad2d_bwd(_dt(dy), dy.contiguous().data_ptr(), dx.data_ptr(), B, H, W, Cc, ctx.pad, _st()),
-              "jg_reflect_pad2d_bwd")
-        return dx, None
+        return launch.reflect_pad2d_bwd(dy.contiguous(), ctx.pad), None
 
 
 def reflect_pad2d(x, pad):
@@ -920,9 +895,7 @@ class _ActFn(JGFunction):
     @staticmethod
     def forward(ctx, x, act):
         _require_cuda(x)
-        x = x.contiguous()
-        y = torch.empty_like(x)
-        check(_lib.lib().jg_act_fwd(_dt(x), x.data_ptr(), y.data_ptr(), x.numel(), act, _st()), "jg_act_fwd")
+        y = launch.act_fwd(x.contiguous(), act)
         ctx.save_for_backward(y)
         ctx.act = act
         return y
@@ -931,10 +904,7 @@ class _ActFn(JGFunction):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = torch.empty_like(y)
-        check(_lib.lib().jg_act_bwd(_dt(y), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), y.numel(), ctx.act, _st()), "jg_act_bwd")
-        return dx, None
+        return launch.act_bwd(y, dy.contiguous(), ctx.act), None
 
 
 def activation(x, act):
@@ -1143,11 +1113,7 @@ class _LinearFn(JGFunction):
     def forward(ctx, x, W, b, act, dW, db, *track):
         _require_cuda(x, W)
         x = x.contiguous()
-        Bn, K = x.shape
-        N = W.shape[0]
-        y = torch.empty((Bn, N), device=x.device, dtype=torch.float32)
-        check(_lib.lib().jg_linear_fwd(x.data_ptr(), W.data_ptr(), _p(b), y.data_ptr(), Bn, K, N, act, _st()),
-              "jg_linear_fwd")
+        y = launch.linear_fwd(x, W, b, act)
         ctx.save_for_backward(x, W)
         ctx.act, ctx.dW, ctx.db = act, dW, db
         ctx.want_param = any(t is not None and t.requires_grad for t in track)
@@ -1159,17 +1125,13 @@ class _LinearFn(JGFunction):
     def backward(ctx, dy):
         x, W = ctx.saved_tensors
         dy = dy.contiguous()
-        Bn, K = x.shape
-        N = W.shape[0]
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dW = db = None
+        dx = dW = db = None
         if ctx.want_param:
             dW, db = ctx.dW, ctx.db
             if dW is None:
                 raise RuntimeError("linear weight has no arena-backed .grad")
-        if dx is not None or dW is not None:
-            check(_lib.lib().jg_linear_bwd(x.data_ptr(), W.data_ptr(), dy.data_ptr(), _p(dx), _p(dW), _p(db), Bn, K, N,
-                                           ctx.act, _st()), "jg_linear_bwd")
+        if ctx.needs_input_grad[0] or dW is not None:
+            dx = launch.linear_bwd(x, W, dy, ctx.act, dW, db, ctx.needs_input_grad[0])
         return (dx, None, None, None, None, None) + (None,) * ctx.ntrack
 
 
@@ -1200,14 +1162,6 @@ def gamma_embedding(gammas, dim, max_period=10000.0):
 # ======================================================================================
 # CUT patch features and contrastive / adversarial losses (fp32)
 # ======================================================================================
-def sgemm(A, B, C, M, N, K, sa, sb, sc, nbatch=1, bstr=(0, 0, 0), bias=None, E=None, alpha=1.0, beta=0.0,
-          act_a=JG_ACT_NONE, act_b=JG_ACT_NONE, act_e=JG_ACT_NONE):
-    """C[z][m][n] = alpha sum_k actA(A[z][m][k]) actB(B[z][n][k]) (+bias, *act'(E), +beta C); sa=(sam,sak), sb=(sbn,sbk), sc=(scm,scn)."""
-    check(_lib.lib().jg_sgemm(A.data_ptr(), B.data_ptr(), C.data_ptr(), _p(bias), _p(E), M, N, K, sa[0], sa[1], sb[0], sb[1],
-                              sc[0], sc[1], nbatch, bstr[0], bstr[1], bstr[2], alpha, beta, act_a, act_b, act_e, _st()), "jg_sgemm")
-    return C
-
-
 class _GatherPatchesFn(JGFunction):
     @staticmethod
     def forward(ctx, feat, ids, C, per):
@@ -1251,11 +1205,7 @@ def gather_patches(feat, ids, C, per=0):
 class _L2NormFn(JGFunction):
     @staticmethod
     def forward(ctx, x, eps):
-        x = x.contiguous()
-        R, D = x.shape
-        y = torch.empty_like(x)
-        nrm = torch.empty(R, device=x.device, dtype=torch.float32)
-        check(_lib.lib().jg_l2norm_fwd(x.data_ptr(), y.data_ptr(), nrm.data_ptr(), R, D, eps, _st()), "jg_l2norm_fwd")
+        y, nrm = launch.l2norm_fwd(x.contiguous(), eps)
         ctx.save_for_backward(y, nrm)
         ctx.eps = eps
         return y
@@ -1264,11 +1214,7 @@ class _L2NormFn(JGFunction):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         y, nrm = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = torch.empty_like(y)
-        check(_lib.lib().jg_l2norm_bwd(y.data_ptr(), nrm.data_ptr(), dy.data_ptr(), dx.data_ptr(), y.shape[0], y.shape[1], ctx.eps,
-                                       _st()), "jg_l2norm_bwd")
-        return dx, None
+        return launch.l2norm_bwd(y, nrm, dy.contiguous(), ctx.eps), None
 
 
 def l2_normalize(x, eps=1e-7):
@@ -1276,9 +1222,6 @@ def l2_normalize(x, eps=1e-7):
     if TORCH_OPS_BOUNDARY:
         return torch.ops.jg355.l2_normalize(x, eps)[0]
     return _L2NormFn.apply(x, eps)
-
-
-SINKHORN_ITERS = 50  # monce.py:24
 
 
 class _PatchNCEFn(JGFunction):
@@ -1289,55 +1232,15 @@ class _PatchNCEFn(JGFunction):
     def forward(ctx, q, k, nimg, T, pm1, monce):
         _require_cuda(q, k)
         q, k = q.contiguous(), k.contiguous()
-        R, D = q.shape
-        P = R // nimg
-        L = _lib.lib()
-        S = torch.empty((nimg, P, P), device=q.device, dtype=torch.float32)
-        sgemm(q, k, S, P, P, D, (D, 1), (D, 1), (P, 1), nimg, (P * D, P * D, P * P))
-        loss = torch.empty(R, device=q.device, dtype=torch.float32)
-        K = uh = vh = None
-        if monce:
-            K = torch.empty_like(S)
-            uh = torch.empty((nimg, SINKHORN_ITERS, P), device=q.device, dtype=torch.float32)
-            vh = torch.empty((nimg, SINKHORN_ITERS + 1, P), device=q.device, dtype=torch.float32)
-            check(L.jg_nce_sinkhorn_fwd(S.data_ptr(), K.data_ptr(), uh.data_ptr(), vh.data_ptr(), nimg, P, SINKHORN_ITERS, 1.0, _st()),
-                  "jg_nce_sinkhorn_fwd")
-        u = uh[:, -1] if monce else None
-        v = vh[:, -1] if monce else None
-        check(L.jg_nce_ce(S.data_ptr(), _p(u), SINKHORN_ITERS * P, _p(v), (SINKHORN_ITERS + 1) * P, loss.data_ptr(), None, None,
-                          nimg, P, T, pm1, None, None, 1.0, _st()), "jg_nce_ce")
+        loss, S, K, uh, vh = launch.nce_fwd(q, k, nimg, T, pm1, monce)
         ctx.save_for_backward(q, k, S, K, uh, vh)
-        ctx.cfg = (nimg, P, D, T, pm1, monce)
+        ctx.cfg = (nimg, T, pm1, monce)
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dloss):
-        q, k, S, K, uh, vh = ctx.saved_tensors
-        nimg, P, D, T, pm1, monce = ctx.cfg
-        L = _lib.lib()
-        dloss = dloss.contiguous().float()
-        dS = torch.empty_like(S)
-        gW = torch.empty_like(S) if monce else None
-        gpos = torch.empty(nimg * P, device=q.device, dtype=torch.float32)
-        scratch = torch.empty_like(q)
-        u = uh[:, -1] if monce else None
-        v = vh[:, -1] if monce else None
-        check(L.jg_nce_ce(S.data_ptr(), _p(u), SINKHORN_ITERS * P, _p(v), (SINKHORN_ITERS + 1) * P, scratch.data_ptr(), dS.data_ptr(),
-                          _p(gW), nimg, P, T, pm1, dloss.data_ptr(), gpos.data_ptr(), 1.0, _st()), "jg_nce_ce")
-        dk = None
-        if ctx.needs_input_grad[1]:
-            # dk_j = sum_i dS_ij q_i over the negatives only (diagonal of dS is zero, the positive pair is detached)
-            dk = torch.empty_like(k)
-            sgemm(dS, q, dk, P, D, P, (1, P), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
-        if monce:
-            dsh = torch.empty_like(uh)
-            drh = torch.empty_like(uh)
-            check(L.jg_nce_sinkhorn_bwd(K.data_ptr(), uh.data_ptr(), vh.data_ptr(), gW.data_ptr(), dsh.data_ptr(), drh.data_ptr(),
-                                        dS.data_ptr(), nimg, P, SINKHORN_ITERS, _st()), "jg_nce_sinkhorn_bwd")
-        dq = torch.empty_like(q)
-        sgemm(dS, k, dq, P, D, P, (P, 1), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
-        check(L.jg_row_axpy(dq.data_ptr(), gpos.data_ptr(), k.data_ptr(), nimg * P, D, _st()), "jg_row_axpy")
+        dq, dk = launch.nce_bwd(*ctx.saved_tensors, dloss.contiguous().float(), *ctx.cfg, want_dk=ctx.needs_input_grad[1])
         return dq, dk, None, None, None, None
 
 
@@ -1346,22 +1249,6 @@ def patch_nce_loss(q, k, nimg, T, num_patches, monce=False):
     if TORCH_OPS_BOUNDARY:
         return torch.ops.jg355.patch_nce(q, k, nimg, float(T), float(num_patches - 1), bool(monce))[0]
     return _PatchNCEFn.apply(q, k, nimg, float(T), float(num_patches - 1), bool(monce))
-
-
-def _hdce_gram(k, nimg, P, D, wperiod, wcount):
-    """k k^T of the problems whose weights are needed: the leading `wcount` problems when there is a single weighted run, else every problem in
-    ONE launch (the weighted runs are not a strided batch; the kernel never reads the Gram matrix of an unweighted problem)"""
-    if wcount < 1:
-        return None
-    ng = min(wcount, nimg) if wperiod >= nimg else nimg
-    G = torch.empty((ng, P, P), device=k.device, dtype=torch.float32)
-    sgemm(k, k, G, P, P, D, (D, 1), (D, 1), (P, 1), ng, (P * D, P * D, P * P))
-    return G
-
-
-def _hdce_check(nimg, R, gamma, wperiod, wcount):
-    if nimg < 1 or R % nimg or not gamma > 0 or wperiod < 1 or not 0 <= wcount <= wperiod:
-        raise ValueError(f"patch_hdce: nimg={nimg} rows={R} gamma={gamma} wperiod={wperiod} wcount={wcount}")
 
 
 class _PatchHDCEFn(JGFunction):
@@ -1373,38 +1260,15 @@ class _PatchHDCEFn(JGFunction):
     def forward(ctx, q, k, nimg, T, gamma, wperiod, wcount):
         _require_cuda(q, k)
         q, k = q.contiguous(), k.contiguous()
-        R, D = q.shape
-        _hdce_check(nimg, R, gamma, wperiod, wcount)
-        P = R // nimg
-        S = torch.empty((nimg, P, P), device=q.device, dtype=torch.float32)
-        sgemm(q, k, S, P, P, D, (D, 1), (D, 1), (P, 1), nimg, (P * D, P * D, P * P))
-        G = _hdce_gram(k, nimg, P, D, wperiod, wcount)
-        loss = torch.empty(R, device=q.device, dtype=torch.float32)
-        stats = torch.empty((3, R), device=q.device, dtype=torch.float32)
-        check(_lib.lib().jg_nce_hdce(S.data_ptr(), _p(G), stats.data_ptr(), loss.data_ptr(), None, None, None, None, nimg, P, T, gamma, wperiod,
-                                     wcount, _st()), "jg_nce_hdce")
+        loss, S, G, stats = launch.hdce_fwd(q, k, nimg, T, gamma, wperiod, wcount)
         ctx.save_for_backward(q, k, S, G, stats)
-        ctx.cfg = (nimg, P, D, T, gamma, wperiod, wcount)
+        ctx.cfg = (nimg, T, gamma, wperiod, wcount)
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dloss):
-        q, k, S, G, stats = ctx.saved_tensors
-        nimg, P, D, T, gamma, wperiod, wcount = ctx.cfg
-        L = _lib.lib()
-        dloss = dloss.contiguous().float()
-        dS = torch.empty_like(S)
-        gpos = torch.empty(nimg * P, device=q.device, dtype=torch.float32)
-        check(L.jg_nce_hdce(S.data_ptr(), _p(G), stats.data_ptr(), None, dS.data_ptr(), gpos.data_ptr(), dloss.data_ptr(), None, nimg, P, T, gamma,
-                            wperiod, wcount, _st()), "jg_nce_hdce")
-        dk = None
-        if ctx.needs_input_grad[1]:
-            dk = torch.empty_like(k)
-            sgemm(dS, q, dk, P, D, P, (1, P), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
-        dq = torch.empty_like(q)
-        sgemm(dS, k, dq, P, D, P, (P, 1), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
-        check(L.jg_row_axpy(dq.data_ptr(), gpos.data_ptr(), k.data_ptr(), nimg * P, D, _st()), "jg_row_axpy")
+        dq, dk = launch.hdce_bwd(*ctx.saved_tensors, dloss.contiguous().float(), *ctx.cfg, want_dk=ctx.needs_input_grad[1])
         return dq, dk, None, None, None, None, None
 
 
@@ -1419,16 +1283,7 @@ def patch_hdce_loss(q, k, nimg, T, gamma, wperiod=1, wcount=1):
 def hdce_weights(k, nimg, gamma):
     """the hDCE weights [nimg, P, P] of SRC_Loss(only_weight=True) with a zero diagonal (tests / inspection: training never stores them)"""
     _require_cuda(k)
-    k = k.detach().contiguous()
-    R, D = k.shape
-    _hdce_check(nimg, R, gamma, 1, 1)
-    P = R // nimg
-    G = _hdce_gram(k, nimg, P, D, 1, 1)
-    W = torch.empty_like(G)
-    scratch = torch.empty((4, R), device=k.device, dtype=torch.float32)
-    check(_lib.lib().jg_nce_hdce(G.data_ptr(), G.data_ptr(), scratch.data_ptr(), scratch[3].data_ptr(), None, None, None, W.data_ptr(), nimg, P, 1.0,
-                                 float(gamma), 1, 1, _st()), "jg_nce_hdce")
-    return W
+    return launch.hdce_weights(k.detach().contiguous(), nimg, gamma)
 
 
 GAN_MODES = {"lsgan": 0, "vanilla": 1, "wgangp": 2}
@@ -1438,14 +1293,7 @@ class _LSGANLossFn(JGFunction):
     @staticmethod
     def forward(ctx, pred, target, scale, mode=0):
         _require_cuda(pred)
-        pred = pred.contiguous()
-        cpad = pred.shape[-1]
-        npix = pred.numel() // cpad
-        loss = torch.zeros((), device=pred.device, dtype=torch.float32)
-        dpred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
-        check(_lib.lib().jg_gan_loss(_dt(pred), mode, pred.data_ptr(), target, loss.data_ptr(), _p(dpred), npix, cpad, scale, 1.0, _st()),
-              "jg_gan_loss")
-        ctx.dpred = dpred
+        loss, ctx.dpred = launch.gan_loss(pred.contiguous(), mode, target, scale, ctx.needs_input_grad[0])
         return loss
 
     @staticmethod
@@ -1533,11 +1381,7 @@ def lowres_roundtrip(x, scale_or_size, out=None):
 class _MSELossFn(JGFunction):
     @staticmethod
     def forward(ctx, nh, noise, mask, w, lam, grad_scale, Cc):
-        B, H, W, cpad = nh.shape
-        loss = torch.zeros((), device=nh.device, dtype=torch.float32)
-        dnh = torch.empty_like(nh)
-        check(_lib.lib().jg_ddpm_mse_loss(_dt(nh), noise.data_ptr(), nh.data_ptr(), _p(mask), _p(w), loss.data_ptr(),
-                                          dnh.data_ptr(), B, Cc, H, W, cpad, lam, grad_scale, _st()), "jg_ddpm_mse_loss")
+        loss, dnh = launch.ddpm_mse_loss(nh, noise, mask, w, lam, grad_scale, Cc)
         ctx.save_for_backward(dnh)
         return loss
 
@@ -2358,15 +2202,7 @@ _op_conv2d_nt.register_autograd(_conv2d_nt_backward, setup_context=_conv2d_nt_se
 def _op_group_norm_act(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], film: Optional[torch.Tensor],
                        groups: int, act: int, eps: float) -> torch.Tensor:
     """act(GroupNorm_groups(x) gamma + beta [(1 + scale) + shift]); x NHWC 16-bit (any number of middle dims), film fp32 [B, 2C]"""
-    return _GroupNormFn.forward(_NoCtx(), x.contiguous(), gamma, beta, None if film is None else film.contiguous(), groups, act, eps)
-
-
-class _NoCtx:
-    """stand-in autograd context for calling a Function's forward as a plain kernel sequence"""
-    needs_input_grad = (False,) * 8
-
-    def save_for_backward(self, *a):
-        self.saved = a
+    return _group_norm_launch(x.contiguous(), gamma, beta, None if film is None else film.contiguous(), groups, act, eps)[0]
 
 
 @_op_group_norm_act.register_fake
@@ -2495,12 +2331,7 @@ _op_resample2.register_autograd(_resample_backward, setup_context=_resample_setu
 @torch.library.custom_op("jg355::linear_act", mutates_args=())
 def _op_linear_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: int) -> torch.Tensor:
     """y = act(x) @ weight.T + bias, fp32 (`emb_layers` / `cond_embed` of the UNet: nn.Linear behind an optional SiLU)"""
-    x, weight = x.contiguous(), weight.contiguous()
-    Bn, K = x.shape
-    N = weight.shape[0]
-    y = torch.empty((Bn, N), device=x.device, dtype=torch.float32)
-    check(_lib.lib().jg_linear_fwd(x.data_ptr(), weight.data_ptr(), _p(bias), y.data_ptr(), Bn, K, N, act, _st()), "jg_linear_fwd")
-    return y
+    return launch.linear_fwd(x.contiguous(), weight.contiguous(), bias, act)
 
 
 @_op_linear_act.register_fake
@@ -2511,12 +2342,8 @@ def _(x, weight, bias, act):
 @torch.library.custom_op("jg355::linear_act_bwd", mutates_args=())
 def _op_linear_act_bwd(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, act: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     x, weight, dy = x.contiguous(), weight.contiguous(), dy.contiguous()
-    Bn, K = x.shape
-    N = weight.shape[0]
-    dx, dW, db = torch.empty_like(x), torch.zeros_like(weight), torch.zeros((N,), device=x.device, dtype=torch.float32)
-    check(_lib.lib().jg_linear_bwd(x.data_ptr(), weight.data_ptr(), dy.data_ptr(), dx.data_ptr(), dW.data_ptr(), db.data_ptr(), Bn, K, N, act,
-                                   _st()), "jg_linear_bwd")
-    return dx, dW, db
+    dW, db = torch.zeros_like(weight), torch.zeros((weight.shape[0],), device=x.device, dtype=torch.float32)
+    return launch.linear_bwd(x, weight, dy, act, dW, db), dW, db
 
 
 @_op_linear_act_bwd.register_fake
@@ -2659,13 +2486,7 @@ _op_cm_gan_head.register_autograd(_cm_gan_head_backward, setup_context=_cm_gan_h
 def _op_ddpm_mse_loss(nh: torch.Tensor, noise: torch.Tensor, mask: Optional[torch.Tensor], w: Optional[torch.Tensor], lam: float,
                       grad_scale: float, channels: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """(lambda MSE(w m noise, w m noise_hat), its gradient w.r.t. noise_hat times grad_scale) in one pass (palette_model.py:597-620)"""
-    B, H, W, cpad = nh.shape
-    nh = nh.contiguous()
-    loss = torch.zeros((), device=nh.device, dtype=torch.float32)
-    dnh = torch.empty_like(nh)
-    check(_lib.lib().jg_ddpm_mse_loss(_dt(nh), noise.contiguous().data_ptr(), nh.data_ptr(), _p(mask), _p(w), loss.data_ptr(), dnh.data_ptr(), B,
-                                      channels, H, W, cpad, lam, grad_scale, _st()), "jg_ddpm_mse_loss")
-    return loss, dnh
+    return launch.ddpm_mse_loss(nh.contiguous(), noise.contiguous(), mask, w, lam, grad_scale, channels)
 
 
 @_op_ddpm_mse_loss.register_fake

@@ -5,7 +5,9 @@ Every op here is a torch.library custom op over the C ABI of include/jg355.h wit
 other jg355 ops, so it traces (FakeTensor / torch.compile), composes with autograd and passes torch.library.opcheck
 (tests/test_gpu_0_ops.py::test_torch_ops_surface_cut).  The ops are FUNCTIONAL: parameter gradients are RETURNED as fresh tensors (the
 module graph's arena-accumulating nodes add them in place; `ops.torch_ops_boundary()` switches the modules to these ops, and
-tests/test_gpu_5_cutloss.py::test_cut_step_through_torch_ops holds the two forms together on one CUT step).
+tests/test_gpu_5_cutloss.py::test_cut_step_through_torch_ops holds the two forms together on one CUT step).  The launches themselves are
+the helpers of launch.py, the same ones the module graph calls: an op here is a schema, a fake kernel and an autograd formula; it makes its
+inputs contiguous, hands fresh zeros to the accumulating kernels and turns a None output into the empty tensor its schema needs (`_z`).
 
   layer_norm / layer_norm_bwd                nn.LayerNorm of the SegFormer blocks and the ViT projector
   dwconv3x3_gelu / _bwd                      MixFFN's depth-wise 3x3 (+ GELU)
@@ -30,10 +32,10 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, launch, ops
 from ._lib import check
-from . import ops
-from .ops import SINKHORN_ITERS, _DT, _dt, _p, _st, conv_nt, sgemm, wgrad_tn
+from .launch import SINKHORN_ITERS, _DT, _dt, _st
+from .ops import conv_nt, wgrad_tn
 
 T = torch.Tensor
 op = torch.library.custom_op
@@ -47,14 +49,7 @@ def _z(like, dtype=torch.float32):
 @op("jg355::layer_norm", mutates_args=())
 def layer_norm(x: T, weight: T, bias: T, eps: float) -> Tuple[T, T]:
     """nn.LayerNorm(C, eps) over the last dimension of a 16-bit tensor -> (y, mr [rows, 2] = mean | rstd saved for the backward)"""
-    x = x.contiguous()
-    C = x.shape[-1]
-    R = x.numel() // C
-    y = torch.empty_like(x)
-    mr = torch.empty((R, 2), device=x.device, dtype=torch.float32)
-    check(_lib.lib().jg_layernorm_fwd(_dt(x), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mr.data_ptr(), R, C, eps, _st()),
-          "jg_layernorm_fwd")
-    return y, mr
+    return launch.layernorm_fwd(x.contiguous(), weight, bias, eps)
 
 
 @layer_norm.register_fake
@@ -64,13 +59,9 @@ def _(x, weight, bias, eps):
 
 @op("jg355::layer_norm_bwd", mutates_args=())
 def layer_norm_bwd(x: T, dy: T, weight: T, mr: T) -> Tuple[T, T, T]:
-    x, dy = x.contiguous(), dy.contiguous()
     C = x.shape[-1]
-    dx = torch.empty_like(x)
     dg, db = torch.zeros(C, device=x.device, dtype=torch.float32), torch.zeros(C, device=x.device, dtype=torch.float32)
-    check(_lib.lib().jg_layernorm_bwd(_dt(x), x.data_ptr(), dy.data_ptr(), weight.data_ptr(), mr.data_ptr(), dx.data_ptr(), dg.data_ptr(),
-                                      db.data_ptr(), x.numel() // C, C, _st()), "jg_layernorm_bwd")
-    return dx, dg, db
+    return launch.layernorm_bwd(x.contiguous(), dy.contiguous(), weight, mr, dg, db), dg, db
 
 
 @layer_norm_bwd.register_fake
@@ -97,14 +88,8 @@ layer_norm.register_autograd(_ln_backward, setup_context=_ln_setup)
 @op("jg355::dwconv3x3_gelu", mutates_args=())
 def dwconv3x3_gelu(x: T, weight: T, bias: Optional[T], gelu: bool) -> Tuple[T, T]:
     """nn.Conv2d(C, C, 3, padding=1, groups=C) (+ nn.GELU()) on an NHWC map; weight fp32 [C, 1, 3, 3] -> (y, pre-activation; empty without gelu)"""
-    x = x.contiguous()
-    B, H, W, C = x.shape
-    y = torch.empty_like(x)
-    pre = torch.empty_like(x) if gelu else _z(x, x.dtype)
-    w = weight.contiguous()
-    check(_lib.lib().jg_dwconv3x3_fwd(_dt(x), x.data_ptr(), w.data_ptr(), _p(bias), pre.data_ptr() if gelu else None, y.data_ptr(), B, H, W, C,
-                                      int(gelu), _st()), "jg_dwconv3x3_fwd")
-    return y, pre
+    y, pre = launch.dwconv3x3_fwd(x.contiguous(), weight.contiguous(), bias, gelu)
+    return y, (pre if gelu else _z(x, x.dtype))
 
 
 @dwconv3x3_gelu.register_fake
@@ -114,14 +99,10 @@ def _(x, weight, bias, gelu):
 
 @op("jg355::dwconv3x3_gelu_bwd", mutates_args=())
 def dwconv3x3_gelu_bwd(x: T, pre: T, dy: T, weight: T, gelu: bool) -> Tuple[T, T, T]:
-    x, dy = x.contiguous(), dy.contiguous()
-    B, H, W, C = x.shape
-    du, dx = torch.empty_like(x), torch.empty_like(x)
+    C = x.shape[-1]
     dw = torch.zeros((C, 1, 3, 3), device=x.device, dtype=torch.float32)
     db = torch.zeros(C, device=x.device, dtype=torch.float32)
-    check(_lib.lib().jg_dwconv3x3_bwd(_dt(x), x.data_ptr(), pre.data_ptr() if gelu else None, dy.data_ptr(), weight.contiguous().data_ptr(),
-                                      du.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), B, H, W, C, int(gelu), _st()), "jg_dwconv3x3_bwd")
-    return dx, dw, db
+    return launch.dwconv3x3_bwd(x.contiguous(), pre if gelu else None, dy.contiguous(), weight.contiguous(), dw, db, gelu), dw, db
 
 
 @dwconv3x3_gelu_bwd.register_fake
@@ -149,15 +130,7 @@ dwconv3x3_gelu.register_autograd(_dw_backward, setup_context=_dw_setup)
 @op("jg355::attention_smallkv", mutates_args=())
 def attention_smallkv(q: T, kv: T, heads: int) -> Tuple[T, T]:
     """q [B, Tq, C], kv [B, Tkv, 2C] packed (k | v), head dim 32 -> (o [B, Tq, C], logsumexp [B, heads, Tq])"""
-    q, kv = q.contiguous(), kv.contiguous()
-    B, Tq, C = q.shape
-    Tkv = kv.shape[1]
-    o = torch.empty_like(q)
-    lse = torch.empty((B, heads, Tq), device=q.device, dtype=torch.float32)
-    es = q.element_size()
-    check(_lib.lib().jg_attn_smallkv_fwd(_dt(q), q.data_ptr(), kv.data_ptr(), kv.data_ptr() + C * es, o.data_ptr(), lse.data_ptr(), B, Tq, Tkv, heads, C,
-                                         2 * C, C, 1.0 / 32.0 ** 0.5, _st()), "jg_attn_smallkv_fwd")
-    return o, lse
+    return launch.attn_smallkv_fwd(q.contiguous(), kv.contiguous(), heads)
 
 
 @attention_smallkv.register_fake
@@ -167,17 +140,7 @@ def _(q, kv, heads):
 
 @op("jg355::attention_smallkv_bwd", mutates_args=())
 def attention_smallkv_bwd(q: T, kv: T, o: T, lse: T, do: T, heads: int) -> Tuple[T, T]:
-    q, kv, do = q.contiguous(), kv.contiguous(), do.contiguous()
-    B, Tq, C = q.shape
-    Tkv = kv.shape[1]
-    dq = torch.empty_like(q)
-    acc = torch.empty((2, B, Tkv, C), device=q.device, dtype=torch.float32)
-    dkv = torch.empty_like(kv)
-    es = q.element_size()
-    check(_lib.lib().jg_attn_smallkv_bwd2(_dt(q), q.data_ptr(), kv.data_ptr(), kv.data_ptr() + C * es, o.data_ptr(), do.data_ptr(), lse.data_ptr(),
-                                          dq.data_ptr(), acc[0].data_ptr(), acc[1].data_ptr(), dkv.data_ptr(), dkv.data_ptr() + C * es, 2 * C, B, Tq, Tkv,
-                                          heads, C, 2 * C, C, 1.0 / 32.0 ** 0.5, _st()), "jg_attn_smallkv_bwd2")
-    return dq, dkv
+    return launch.attn_smallkv_bwd(q.contiguous(), kv.contiguous(), o, lse, do.contiguous(), heads)
 
 
 @attention_smallkv_bwd.register_fake
@@ -203,9 +166,7 @@ attention_smallkv.register_autograd(_skv_backward, setup_context=_skv_setup)
 @op("jg355::vit_attention", mutates_args=())
 def vit_attention(qkv: T, heads: int) -> Tuple[T, T]:
     """timm Attention core on the packed projection [B, T, 3C] (channel order [3][heads][head_dim], head dim 32 / 64, any T) -> (a, logsumexp)"""
-    from .modules.projected_d_vit import vit_attention_fwd
-
-    return vit_attention_fwd(qkv.contiguous(), heads)
+    return launch.vit_attention_fwd(qkv.contiguous(), heads)
 
 
 @vit_attention.register_fake
@@ -216,9 +177,7 @@ def _(qkv, heads):
 
 @op("jg355::vit_attention_bwd", mutates_args=())
 def vit_attention_bwd(qkv: T, a: T, lse: T, da: T, heads: int) -> T:
-    from .modules.projected_d_vit import vit_attention_bwd as bwd
-
-    return bwd(qkv.contiguous(), a, lse, da.contiguous(), heads)
+    return launch.vit_attention_bwd(qkv.contiguous(), a, lse, da.contiguous(), heads)
 
 
 @vit_attention_bwd.register_fake
@@ -241,10 +200,7 @@ vit_attention.register_autograd(_va_backward, setup_context=_va_setup)
 
 @op("jg355::gelu", mutates_args=())
 def gelu(x: T) -> T:
-    x = x.contiguous()
-    y = torch.empty_like(x)
-    check(_lib.lib().jg_gelu_fwd(_dt(x), x.data_ptr(), y.data_ptr(), x.numel(), _st()), "jg_gelu_fwd")
-    return y
+    return launch.gelu_fwd(x.contiguous())
 
 
 @gelu.register_fake
@@ -254,10 +210,7 @@ def _(x):
 
 @op("jg355::gelu_bwd", mutates_args=())
 def gelu_bwd(x: T, dy: T) -> T:
-    x, dy = x.contiguous(), dy.contiguous()
-    dx = torch.empty_like(x)
-    check(_lib.lib().jg_gelu_bwd(_dt(x), x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), _st()), "jg_gelu_bwd")
-    return dx
+    return launch.gelu_bwd(x.contiguous(), dy.contiguous())
 
 
 @gelu_bwd.register_fake
@@ -272,11 +225,7 @@ gelu.register_autograd(lambda ctx, dy: torch.ops.jg355.gelu_bwd(ctx.saved_tensor
 # ---- padding / dilation / activation ----------------------------------------------------------------------------------------------------
 @op("jg355::reflect_pad2d", mutates_args=())
 def reflect_pad2d(x: T, pad: int) -> T:
-    x = x.contiguous()
-    B, H, W, C = x.shape
-    y = torch.empty((B, H + 2 * pad, W + 2 * pad, C), device=x.device, dtype=x.dtype)
-    check(_lib.lib().jg_reflect_pad2d(_dt(x), x.data_ptr(), y.data_ptr(), B, H, W, C, pad, _st()), "jg_reflect_pad2d")
-    return y
+    return launch.reflect_pad2d(x.contiguous(), pad)
 
 
 @reflect_pad2d.register_fake
@@ -288,12 +237,7 @@ def _(x, pad):
 @op("jg355::reflect_pad2d_bwd", mutates_args=())
 def reflect_pad2d_bwd(dy: T, pad: int) -> T:
     """adjoint of ReflectionPad2d(pad): dy [B, H + 2 pad, W + 2 pad, C] folded back onto [B, H, W, C]"""
-    dy = dy.contiguous()
-    B, Hp, Wp, C = dy.shape
-    H, W = Hp - 2 * pad, Wp - 2 * pad
-    dx = torch.empty((B, H, W, C), device=dy.device, dtype=dy.dtype)
-    check(_lib.lib().jg_reflect_pad2d_bwd(_dt(dy), dy.data_ptr(), dx.data_ptr(), B, H, W, C, pad, _st()), "jg_reflect_pad2d_bwd")
-    return dx
+    return launch.reflect_pad2d_bwd(dy.contiguous(), pad)
 
 
 @reflect_pad2d_bwd.register_fake
@@ -333,10 +277,7 @@ dilate2d.register_autograd(_dil_backward, setup_context=_dil_setup)
 
 @op("jg355::act", mutates_args=())
 def act(x: T, kind: int) -> T:
-    x = x.contiguous()
-    y = torch.empty_like(x)
-    check(_lib.lib().jg_act_fwd(_dt(x), x.data_ptr(), y.data_ptr(), x.numel(), kind, _st()), "jg_act_fwd")
-    return y
+    return launch.act_fwd(x.contiguous(), kind)
 
 
 @act.register_fake
@@ -346,10 +287,7 @@ def _(x, kind):
 
 @op("jg355::act_bwd", mutates_args=())
 def act_bwd(y: T, dy: T, kind: int) -> T:
-    y, dy = y.contiguous(), dy.contiguous()
-    dx = torch.empty_like(y)
-    check(_lib.lib().jg_act_bwd(_dt(y), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), y.numel(), kind, _st()), "jg_act_bwd")
-    return dx
+    return launch.act_bwd(y.contiguous(), dy.contiguous(), kind)
 
 
 @act_bwd.register_fake
@@ -472,12 +410,7 @@ gather_patches.register_autograd(_gp_backward, setup_context=_gp_setup)
 
 @op("jg355::l2_normalize", mutates_args=())
 def l2_normalize(x: T, eps: float) -> Tuple[T, T]:
-    x = x.contiguous()
-    R, D = x.shape
-    y = torch.empty_like(x)
-    nrm = torch.empty(R, device=x.device, dtype=torch.float32)
-    check(_lib.lib().jg_l2norm_fwd(x.data_ptr(), y.data_ptr(), nrm.data_ptr(), R, D, eps, _st()), "jg_l2norm_fwd")
-    return y, nrm
+    return launch.l2norm_fwd(x.contiguous(), eps)
 
 
 @l2_normalize.register_fake
@@ -487,10 +420,7 @@ def _(x, eps):
 
 @op("jg355::l2_normalize_bwd", mutates_args=())
 def l2_normalize_bwd(y: T, nrm: T, dy: T, eps: float) -> T:
-    dy = dy.contiguous()
-    dx = torch.empty_like(y)
-    check(_lib.lib().jg_l2norm_bwd(y.data_ptr(), nrm.data_ptr(), dy.data_ptr(), dx.data_ptr(), y.shape[0], y.shape[1], eps, _st()), "jg_l2norm_bwd")
-    return dx
+    return launch.l2norm_bwd(y, nrm, dy.contiguous(), eps)
 
 
 @l2_normalize_bwd.register_fake
@@ -511,24 +441,8 @@ l2_normalize.register_autograd(lambda ctx, dy, dn: (torch.ops.jg355.l2_normalize
 def patch_nce(q: T, k: T, nimg: int, temp: float, pm1: float, monce: bool) -> Tuple[T, T, T, T, T]:
     """per-patch PatchNCE / MoNCE loss (base_NCE.py:17-66, monce.py:16-33; Sinkhorn iterations inside): q, k [nimg * P, D] fp32 L2-normalised
     -> (loss [nimg * P], logits S, and the optimal-transport state K, u-history, v-history: empty without monce)"""
-    q, k = q.contiguous(), k.contiguous()
-    R, D = q.shape
-    P = R // nimg
-    L = _lib.lib()
-    S = torch.empty((nimg, P, P), device=q.device, dtype=torch.float32)
-    sgemm(q, k, S, P, P, D, (D, 1), (D, 1), (P, 1), nimg, (P * D, P * D, P * P))
-    loss = torch.empty(R, device=q.device, dtype=torch.float32)
-    K, uh, vh = _z(q), _z(q), _z(q)
-    u = v = None
-    if monce:
-        K = torch.empty_like(S)
-        uh = torch.empty((nimg, SINKHORN_ITERS, P), device=q.device, dtype=torch.float32)
-        vh = torch.empty((nimg, SINKHORN_ITERS + 1, P), device=q.device, dtype=torch.float32)
-        check(L.jg_nce_sinkhorn_fwd(S.data_ptr(), K.data_ptr(), uh.data_ptr(), vh.data_ptr(), nimg, P, SINKHORN_ITERS, 1.0, _st()), "jg_nce_sinkhorn_fwd")
-        u, v = uh[:, -1], vh[:, -1]
-    check(L.jg_nce_ce(S.data_ptr(), _p(u), SINKHORN_ITERS * P, _p(v), (SINKHORN_ITERS + 1) * P, loss.data_ptr(), None, None, nimg, P, temp, pm1, None,
-                      None, 1.0, _st()), "jg_nce_ce")
-    return loss, S, K, uh, vh
+    loss, S, K, uh, vh = launch.nce_fwd(q.contiguous(), k.contiguous(), nimg, temp, pm1, monce)
+    return (loss, S, K, uh, vh) if monce else (loss, S, _z(q), _z(q), _z(q))
 
 
 @patch_nce.register_fake
@@ -543,28 +457,7 @@ def _(q, k, nimg, temp, pm1, monce):
 
 @op("jg355::patch_nce_bwd", mutates_args=())
 def patch_nce_bwd(q: T, k: T, S: T, K: T, uh: T, vh: T, dloss: T, nimg: int, temp: float, pm1: float, monce: bool) -> Tuple[T, T]:
-    L = _lib.lib()
-    R, D = q.shape
-    P = R // nimg
-    dloss = dloss.contiguous().float()
-    dS = torch.empty_like(S)
-    gW = torch.empty_like(S) if monce else None
-    gpos = torch.empty(R, device=q.device, dtype=torch.float32)
-    scratch = torch.empty_like(q)
-    u = uh[:, -1] if monce else None
-    v = vh[:, -1] if monce else None
-    check(L.jg_nce_ce(S.data_ptr(), _p(u), SINKHORN_ITERS * P, _p(v), (SINKHORN_ITERS + 1) * P, scratch.data_ptr(), dS.data_ptr(), _p(gW), nimg, P, temp, pm1,
-                      dloss.data_ptr(), gpos.data_ptr(), 1.0, _st()), "jg_nce_ce")
-    dk = torch.empty_like(k)
-    sgemm(dS, q, dk, P, D, P, (1, P), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
-    if monce:
-        dsh, drh = torch.empty_like(uh), torch.empty_like(uh)
-        check(L.jg_nce_sinkhorn_bwd(K.data_ptr(), uh.data_ptr(), vh.data_ptr(), gW.data_ptr(), dsh.data_ptr(), drh.data_ptr(), dS.data_ptr(), nimg, P,
-                                    SINKHORN_ITERS, _st()), "jg_nce_sinkhorn_bwd")
-    dq = torch.empty_like(q)
-    sgemm(dS, k, dq, P, D, P, (P, 1), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
-    check(L.jg_row_axpy(dq.data_ptr(), gpos.data_ptr(), k.data_ptr(), R, D, _st()), "jg_row_axpy")
-    return dq, dk
+    return launch.nce_bwd(q, k, S, K, uh, vh, dloss.contiguous().float(), nimg, temp, pm1, monce)
 
 
 @patch_nce_bwd.register_fake
@@ -591,17 +484,7 @@ patch_nce.register_autograd(_nce_backward, setup_context=_nce_setup)
 def patch_hdce(q: T, k: T, nimg: int, temp: float, gamma: float, wperiod: int, wcount: int) -> Tuple[T, T, T, T]:
     """per-patch SRC_hDCE loss (NCE/SRC.py:46-75, NCE/hDCE.py:16-38): q, k [nimg * P, D] fp32; problem b is weighted iff (b % wperiod) < wcount
     -> (loss [nimg * P], logits S, key Gram matrix G (empty with wcount == 0), stats [3, nimg * P] = m | A | rinv for the backward)"""
-    q, k = q.contiguous(), k.contiguous()
-    R, D = q.shape
-    ops._hdce_check(nimg, R, gamma, wperiod, wcount)
-    P = R // nimg
-    S = torch.empty((nimg, P, P), device=q.device, dtype=torch.float32)
-    sgemm(q, k, S, P, P, D, (D, 1), (D, 1), (P, 1), nimg, (P * D, P * D, P * P))
-    G = ops._hdce_gram(k, nimg, P, D, wperiod, wcount)
-    loss = torch.empty(R, device=q.device, dtype=torch.float32)
-    stats = torch.empty((3, R), device=q.device, dtype=torch.float32)
-    check(_lib.lib().jg_nce_hdce(S.data_ptr(), _p(G), stats.data_ptr(), loss.data_ptr(), None, None, None, None, nimg, P, temp, gamma, wperiod, wcount,
-                                 _st()), "jg_nce_hdce")
+    loss, S, G, stats = launch.hdce_fwd(q.contiguous(), k.contiguous(), nimg, temp, gamma, wperiod, wcount)
     return loss, S, (_z(q) if G is None else G), stats
 
 
@@ -619,20 +502,7 @@ def _(q, k, nimg, temp, gamma, wperiod, wcount):
 
 @op("jg355::patch_hdce_bwd", mutates_args=())
 def patch_hdce_bwd(q: T, k: T, S: T, G: T, stats: T, dloss: T, nimg: int, temp: float, gamma: float, wperiod: int, wcount: int) -> Tuple[T, T]:
-    L = _lib.lib()
-    R, D = q.shape
-    P = R // nimg
-    dloss = dloss.contiguous().float()
-    dS = torch.empty_like(S)
-    gpos = torch.empty(R, device=q.device, dtype=torch.float32)
-    check(L.jg_nce_hdce(S.data_ptr(), G.data_ptr() if G.numel() else None, stats.data_ptr(), None, dS.data_ptr(), gpos.data_ptr(), dloss.data_ptr(), None,
-                        nimg, P, temp, gamma, wperiod, wcount, _st()), "jg_nce_hdce")
-    dk = torch.empty_like(k)
-    sgemm(dS, q, dk, P, D, P, (1, P), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
-    dq = torch.empty_like(q)
-    sgemm(dS, k, dq, P, D, P, (P, 1), (1, D), (D, 1), nimg, (P * P, P * D, P * D))
-    check(L.jg_row_axpy(dq.data_ptr(), gpos.data_ptr(), k.data_ptr(), R, D, _st()), "jg_row_axpy")
-    return dq, dk
+    return launch.hdce_bwd(q, k, S, G if G.numel() else None, stats, dloss.contiguous().float(), nimg, temp, gamma, wperiod, wcount)
 
 
 @patch_hdce_bwd.register_fake
@@ -812,13 +682,7 @@ def _(p, Tn, a, b, t_epl, loss, num, den, u, key, call):
 @op("jg355::gan_loss", mutates_args=())
 def gan_loss(pred: T, mode: int, target: float, scale: float) -> Tuple[T, T]:
     """GANLoss: mode 0 lsgan, 1 vanilla (BCE with logits), 2 wgangp, on an NHWC logit map whose channel 0 is valid"""
-    pred = pred.contiguous()
-    cpad = pred.shape[-1]
-    loss = torch.zeros((), device=pred.device, dtype=torch.float32)
-    dpred = torch.empty_like(pred)
-    check(_lib.lib().jg_gan_loss(_dt(pred), mode, pred.data_ptr(), target, loss.data_ptr(), dpred.data_ptr(), pred.numel() // cpad, cpad, scale, 1.0, _st()),
-          "jg_gan_loss")
-    return loss, dpred
+    return launch.gan_loss(pred.contiguous(), mode, target, scale)
 
 
 @gan_loss.register_fake
@@ -829,11 +693,7 @@ def _(pred, mode, target, scale):
 @op("jg355::hinge_loss", mutates_args=())
 def hinge_loss(pred: T, mode: int, scale: float) -> Tuple[T, T]:
     """GANLoss("projected"): mode 0 mean relu(1 - p), 1 mean relu(1 + p), 2 mean(-p) over every element"""
-    pred = pred.contiguous()
-    loss = torch.zeros((), device=pred.device, dtype=torch.float32)
-    dpred = torch.empty_like(pred)
-    check(_lib.lib().jg_hinge_loss(_dt(pred), pred.data_ptr(), loss.data_ptr(), dpred.data_ptr(), pred.numel(), 1, 1, mode, scale, 1.0, _st()), "jg_hinge_loss")
-    return loss, dpred
+    return launch.hinge_loss(pred.contiguous(), mode, scale)
 
 
 @hinge_loss.register_fake
@@ -868,9 +728,7 @@ def spectral_weight(weight: T, u: T, v: T, training: bool) -> Tuple[T, T, T, T]:
     un, vn = u.clone(), v.clone()
     sigma = torch.empty(1, device=W.device, dtype=torch.float32)
     if training:
-        ws = torch.empty(K + Cout + 2, device=W.device, dtype=torch.float32)
-        check(_lib.lib().jg_spectral_power_iter(W.data_ptr(), un.data_ptr(), vn.data_ptr(), sigma.data_ptr(), ws.data_ptr(), Cout, RS, K // RS, 1e-12, _st()),
-              "jg_spectral_power_iter")
+        launch.spectral_power_iter(W, un, vn, sigma, Cout, RS, K // RS)
     else:
         sigma.copy_(torch.dot(un, W.reshape(Cout, K) @ vn).reshape(1))
     return W / sigma, un, vn, sigma
@@ -889,9 +747,7 @@ def spectral_weight_bwd(dwsn: T, weight: T, u: T, v: T, sigma: T) -> T:
     K = W.numel() // Cout
     RS = W.shape[1] * W.shape[2] if W.dim() == 4 else 1
     g = torch.zeros_like(W)
-    ws = torch.empty(1, device=W.device, dtype=torch.float32)
-    check(_lib.lib().jg_spectral_wgrad_fix(dwsn.contiguous().float().data_ptr(), W.data_ptr(), u.data_ptr(), v.data_ptr(), sigma.data_ptr(), g.data_ptr(),
-                                           ws.data_ptr(), Cout, RS, K // RS, _st()), "jg_spectral_wgrad_fix")
+    launch.spectral_wgrad_fix(dwsn.contiguous().float(), W, u, v, sigma, g, Cout, RS, K // RS)
     return g
 
 
@@ -915,11 +771,7 @@ spectral_weight.register_autograd(_sw_backward, setup_context=_sw_setup)
 # ---- bilinear resize ---------------------------------------------------------------------------------------------------------------------
 @op("jg355::bilinear2", mutates_args=())
 def bilinear2(x: T, Ho: int, Wo: int, align_corners: bool) -> T:
-    x = x.contiguous()
-    B, H, W, C = x.shape
-    y = torch.empty((B, Ho, Wo, C), device=x.device, dtype=x.dtype)
-    check(_lib.lib().jg_bilinear2_fwd(_dt(x), x.data_ptr(), y.data_ptr(), B, H, W, C, Ho, Wo, C, int(align_corners), _st()), "jg_bilinear2_fwd")
-    return y
+    return launch.bilinear2_fwd(x.contiguous(), Ho, Wo, align_corners)
 
 
 @bilinear2.register_fake
@@ -929,11 +781,7 @@ def _(x, Ho, Wo, align_corners):
 
 @op("jg355::bilinear2_bwd", mutates_args=())
 def bilinear2_bwd(dy: T, H: int, W: int, align_corners: bool) -> T:
-    dy = dy.contiguous()
-    B, Ho, Wo, C = dy.shape
-    dx = torch.empty((B, H, W, C), device=dy.device, dtype=dy.dtype)
-    check(_lib.lib().jg_bilinear2_bwd(_dt(dy), dy.data_ptr(), dx.data_ptr(), B, H, W, C, Ho, Wo, C, int(align_corners), _st()), "jg_bilinear2_bwd")
-    return dx
+    return launch.bilinear2_bwd(dy.contiguous(), H, W, align_corners)
 
 
 @bilinear2_bwd.register_fake

@@ -4,13 +4,12 @@ Activations are NHWC 16-bit ([B, N, C] token sequences are the same memory as [B
 whose `.grad` the backward kernels accumulate into."""
 from __future__ import annotations
 
-import math
 import os
 
 import torch
 
 from ._autograd import JGFunction
-from . import _lib
+from . import _lib, launch
 from ._lib import JG_ACT_NONE, JG_ACT_RELU, check
 from .ops import _DT, _dt, _p, _require_cuda, _st, copy_channels
 
@@ -26,12 +25,7 @@ class _LayerNormFn(JGFunction):
     def forward(ctx, x, weight, bias, eps):
         _require_cuda(x)
         x = x.contiguous()
-        C = x.shape[-1]
-        R = x.numel() // C
-        y = torch.empty_like(x)
-        mr = torch.empty((R, 2), device=x.device, dtype=torch.float32)
-        check(_lib.lib().jg_layernorm_fwd(_dt(x), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mr.data_ptr(), R, C, eps, _st()),
-              "jg_layernorm_fwd")
+        y, mr = launch.layernorm_fwd(x, weight, bias, eps)
         ctx.save_for_backward(x, mr, weight)
         ctx.gw, ctx.gb = weight.grad, bias.grad
         return y
@@ -40,15 +34,10 @@ class _LayerNormFn(JGFunction):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         x, mr, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        C = x.shape[-1]
-        R = x.numel() // C
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         want_p = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         if want_p and (ctx.gw is None or ctx.gb is None):
             raise RuntimeError("LayerNorm parameters have no arena-backed .grad")
-        check(_lib.lib().jg_layernorm_bwd(_dt(x), x.data_ptr(), dy.data_ptr(), weight.data_ptr(), mr.data_ptr(), _p(dx),
-                                          _p(ctx.gw) if want_p else None, _p(ctx.gb) if want_p else None, R, C, _st()), "jg_layernorm_bwd")
+        dx = launch.layernorm_bwd(x, dy.contiguous(), weight, mr, ctx.gw if want_p else None, ctx.gb if want_p else None, ctx.needs_input_grad[0])
         return dx, None, None, None
 
 
@@ -65,12 +54,7 @@ class _LayerNormIdFn(JGFunction):
     def forward(ctx, x, weight, bias, eps):
         _require_cuda(x)
         x = x.contiguous()
-        C = x.shape[-1]
-        R = x.numel() // C
-        y = torch.empty_like(x)
-        mr = torch.empty((R, 2), device=x.device, dtype=torch.float32)
-        check(_lib.lib().jg_layernorm_fwd(_dt(x), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mr.data_ptr(), R, C, eps, _st()),
-              "jg_layernorm_fwd")
+        y, mr = launch.layernorm_fwd(x, weight, bias, eps)
         ctx.save_for_backward(x, mr, weight)
         ctx.gw, ctx.gb = weight.grad, bias.grad
         return x.view_as(x), y
@@ -168,11 +152,7 @@ class _DWConvGeluFn(JGFunction):
     def forward(ctx, x, weight, bias, gelu, reflect=False):
         _require_cuda(x)
         x = x.contiguous()
-        B, H, W, C = x.shape
-        y = torch.empty_like(x)
-        pre = torch.empty_like(x) if gelu else None
-        check(_lib.lib().jg_dwconv3x3_fwd_pad(_dt(x), x.data_ptr(), weight.data_ptr(), _p(bias), _p(pre), y.data_ptr(), B, H, W, C, int(gelu),
-                                              int(reflect), _st()), "jg_dwconv3x3_fwd_pad")
+        y, pre = launch.dwconv3x3_fwd(x, weight, bias, gelu, reflect)
         ctx.save_for_backward(x, pre, weight)
         ctx.gelu, ctx.gw, ctx.gb, ctx.reflect = gelu, weight.grad, None if bias is None else bias.grad, bool(reflect)
         return y
@@ -181,22 +161,13 @@ class _DWConvGeluFn(JGFunction):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         x, pre, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        B, H, W, C = x.shape
-        du = torch.empty_like(x)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         want_w = ctx.needs_input_grad[1]
         if want_w and ctx.gw is None:
             raise RuntimeError("depth-wise conv weight has no arena-backed .grad")
         # weight / bias partials of the blocks go through a workspace and a second launch (DW_TWO_PHASE): straight atomics put a
         # 1024-deep same-address chain on every one of the C * 10 destinations
-        ws, nws = None, 0
-        if want_w and DW_TWO_PHASE:
-            nws = int(_lib.lib().jg_dwconv3x3_bwd_ws_floats(B, H, W, C))
-            ws = torch.empty(nws, device=x.device, dtype=torch.float32)
-        check(_lib.lib().jg_dwconv3x3_bwd_ws_pad(_dt(x), x.data_ptr(), _p(pre), dy.data_ptr(), weight.data_ptr(), du.data_ptr(), _p(dx),
-                                                 _p(ctx.gw) if want_w else None, _p(ctx.gb) if (want_w and ctx.gb is not None) else None, _p(ws), nws,
-                                                 B, H, W, C, int(ctx.gelu), int(ctx.reflect), _st()), "jg_dwconv3x3_bwd_ws_pad")
+        dx = launch.dwconv3x3_bwd(x, pre, dy.contiguous(), weight, ctx.gw if want_w else None, ctx.gb if want_w else None, ctx.gelu, ctx.reflect,
+                                  want_dx=ctx.needs_input_grad[0], two_phase=want_w and DW_TWO_PHASE)
         return dx, None, None, None, None
 
 
@@ -223,14 +194,9 @@ class _AttnSmallKVFn(JGFunction):
     def forward(ctx, q, kv, heads):
         _require_cuda(q, kv)
         q, kv = q.contiguous(), kv.contiguous()
-        B, Tq, C = q.shape
-        Tkv = kv.shape[1]
+        C = q.shape[2]
         assert kv.shape[2] == 2 * C and C == heads * 32, (tuple(kv.shape), C, heads)
-        o = torch.empty_like(q)
-        lse = torch.empty((B, heads, Tq), device=q.device, dtype=torch.float32)
-        es = q.element_size()
-        check(_lib.lib().jg_attn_smallkv_fwd(_dt(q), q.data_ptr(), kv.data_ptr(), kv.data_ptr() + C * es, o.data_ptr(), lse.data_ptr(), B, Tq, Tkv,
-                                             heads, C, 2 * C, C, 1.0 / math.sqrt(32.0), _st()), "jg_attn_smallkv_fwd")
+        o, lse = launch.attn_smallkv_fwd(q, kv, heads)
         ctx.save_for_backward(q, kv, o, lse)
         ctx.heads = heads
         return o
@@ -239,17 +205,7 @@ class _AttnSmallKVFn(JGFunction):
     @torch.autograd.function.once_differentiable
     def backward(ctx, do):
         q, kv, o, lse = ctx.saved_tensors
-        do = do.contiguous()
-        B, Tq, C = q.shape
-        Tkv = kv.shape[1]
-        dq = torch.empty_like(q)
-        acc = torch.empty((2, B, Tkv, C), device=q.device, dtype=torch.float32)       # dk | dv fp32 accumulators: one buffer, one fill
-        dkv = torch.empty((B, Tkv, 2 * C), device=q.device, dtype=q.dtype)             # gradient of the packed kv projection, written in place
-        es = q.element_size()
-        check(_lib.lib().jg_attn_smallkv_bwd2(_dt(q), q.data_ptr(), kv.data_ptr(), kv.data_ptr() + C * es, o.data_ptr(), do.data_ptr(), lse.data_ptr(),
-                                              dq.data_ptr(), acc[0].data_ptr(), acc[1].data_ptr(), dkv.data_ptr(), dkv.data_ptr() + C * es, 2 * C, B, Tq,
-                                              Tkv, ctx.heads, C, 2 * C, C, 1.0 / math.sqrt(32.0), _st()), "jg_attn_smallkv_bwd2")
-        return dq, dkv, None
+        return (*launch.attn_smallkv_bwd(q, kv, o, lse, do.contiguous(), ctx.heads), None)
 
 
 def attention_smallkv(q, kv, heads):
@@ -625,8 +581,7 @@ class _ResizeSumFn(JGFunction):
             return (None, None, (dy if plain else g) if need0 else None) + tuple(outs)
         g = dy
         if act != JG_ACT_NONE:
-            g = torch.empty_like(y)
-            check(_lib.lib().jg_act_bwd(_dt(y), y.data_ptr(), dy.data_ptr(), g.data_ptr(), y.numel(), act, _st()), "jg_act_bwd")
+            g = launch.act_bwd(y, dy, act)
         outs = []
         for i, (_, H, W, _c) in enumerate(shapes):
             dx = None

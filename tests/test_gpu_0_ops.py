@@ -1888,16 +1888,32 @@ def test_torch_ops_surface_cut(dtype):
     layer_norm, dwconv3x3_gelu, attention_smallkv, vit_attention, gelu, reflect_pad2d, reflect_conv2d, dilate2d, act, gather_patches,
     l2_normalize, patch_nce (PatchNCE and MoNCE), gan_loss, hinge_loss, spectral_weight, bilinear2, and a strided conv2d_nt."""
     import jg_oracle as O
-    from joligen_amd import ops  # noqa: F401  (registers the ops)
+    from joligen_amd import launch, ops, ops_segformer  # noqa: F401  (ops registers the ops)
     from joligen_amd._lib import JG_ACT_LRELU
+    from joligen_amd.modules import projected_d
 
     d = dev()
     chk = ("test_schema", "test_faketensor", "test_autograd_registration")
     J = torch.ops.jg355
     tol = TOL[dtype]
+    assert not ops.TORCH_OPS_BOUNDARY
 
     def cmp(mine, ref, f=2.0, msg=""):
         assert relerr(mine, ref) < f * tol, (msg, relerr(mine, ref))
+
+    def same_bits(module_fn, op_fn, msg):
+        """the module graph and the op launch the same kernel (joligen_amd/launch.py): equal bits, where the kernel has neither atomics nor
+        a data-dependent order -- which two calls of the module-graph function establish first"""
+        a, a2, b = module_fn(), module_fn(), op_fn()
+        for i, (t, t2, u) in enumerate(zip(a, a2, b)):
+            assert t.shape == u.shape and t.dtype == u.dtype, (msg, i)
+            assert torch.equal(t, t2), (msg, i, "the module-graph function does not reproduce its own bits")
+            assert torch.equal(t, u), (msg, i, "module graph and torch.ops differ")
+
+    def grad_of(fn, x, gy):
+        xg = x.detach().clone().requires_grad_(True)
+        fn(xg).backward(gy)
+        return xg.grad
 
     # ---- layer_norm
     x = rnd((3, 50, 160), dtype, 1).to(d).requires_grad_(True)
@@ -1909,6 +1925,12 @@ def test_torch_ops_surface_cut(dtype):
     xr, gr, br = (t.detach().float().cpu().requires_grad_(True) for t in (x, gam, bet))
     F.layer_norm(xr, (160,), gr, br, 1e-6).backward(gy.float().cpu())
     cmp(x.grad, xr.grad, msg="ln dx"); cmp(gam.grad, gr.grad, msg="ln dgamma"); cmp(bet.grad, br.grad, msg="ln dbeta")
+
+    def ln_module():
+        y = ops_segformer.layer_norm(x, gam, bet, 1e-6)
+        return y.detach(), y.grad_fn.saved_tensors[1]          # (x, mr, weight) are what the node keeps
+
+    same_bits(ln_module, lambda: tuple(t.detach() for t in J.layer_norm(x, gam, bet, 1e-6)), "layer_norm y, mr")
     # ---- dwconv3x3 + gelu
     x = rnd((2, 12, 10, 64), dtype, 5).to(d).requires_grad_(True)
     w = (rnd((64, 1, 3, 3), torch.float32, 6) / 3).to(d).requires_grad_(True)
@@ -1919,6 +1941,7 @@ def test_torch_ops_surface_cut(dtype):
     xr, wr, br = (t.detach().float().cpu().requires_grad_(True) for t in (x, w, b))
     F.gelu(F.conv2d(xr.permute(0, 3, 1, 2), wr, br, padding=1, groups=64)).backward(gy.float().cpu().permute(0, 3, 1, 2))
     cmp(x.grad, xr.grad, 3.0, "dw dx"); cmp(w.grad, wr.grad, 3.0, "dw dw"); cmp(b.grad, br.grad, 3.0, "dw db")
+    same_bits(lambda: (ops_segformer.dwconv3x3(x, w, b, gelu=True).detach(),), lambda: (J.dwconv3x3_gelu(x, w, b, True)[0].detach(),), "dwconv3x3 + gelu y")
     # ---- attention_smallkv (head dim 32) and vit_attention (head dim 64, 37 tokens)
     q = rnd((2, 96, 64), dtype, 9).to(d).requires_grad_(True)
     kv = rnd((2, 24, 128), dtype, 10).to(d).requires_grad_(True)
@@ -1930,6 +1953,12 @@ def test_torch_ops_surface_cut(dtype):
     kh, vh = kvr[..., :64].reshape(2, 24, 2, 32).transpose(1, 2), kvr[..., 64:].reshape(2, 24, 2, 32).transpose(1, 2)
     ((qh @ kh.transpose(-1, -2) / 32 ** 0.5).softmax(-1) @ vh).transpose(1, 2).reshape(2, 96, 64).backward(go.float().cpu())
     cmp(q.grad, qr.grad, 3.0, "skv dq"); cmp(kv.grad, kvr.grad, 3.0, "skv dkv")
+
+    def skv_module():
+        o = ops_segformer.attention_smallkv(q, kv, 2)
+        return o.detach(), o.grad_fn.saved_tensors[3]          # (q, kv, o, lse)
+
+    same_bits(skv_module, lambda: tuple(t.detach() for t in J.attention_smallkv(q, kv, 2)), "attention_smallkv o, lse")
     qkv = (rnd((2, 37, 3 * 128), dtype, 12).float() * 0.7).to(dtype).to(d).requires_grad_(True)
     ga = rnd((2, 37, 128), dtype, 13).to(d)
     torch.library.opcheck(J.vit_attention.default, (qkv, 2), test_utils=chk)
@@ -1946,12 +1975,16 @@ def test_torch_ops_surface_cut(dtype):
     xr = x.detach().float().cpu().requires_grad_(True)
     F.gelu(xr).backward(gy.float().cpu())
     cmp(x.grad, xr.grad, msg="gelu")
+    xc = x.detach()          # (the ViT node of the module graph calls the launch helpers directly)
+    same_bits(lambda: (launch.gelu_fwd(xc), launch.gelu_bwd(xc, gy)), lambda: (J.gelu(xc), J.gelu_bwd(xc, gy)), "gelu forward, backward")
     x2 = x.detach().clone().requires_grad_(True)
     torch.library.opcheck(J.act.default, (x2, JG_ACT_LRELU), test_utils=chk)
     J.act(x2, JG_ACT_LRELU).backward(gy)
     xr = x.detach().float().cpu().requires_grad_(True)
     F.leaky_relu(xr, 0.2).backward(gy.float().cpu())
     cmp(x2.grad, xr.grad, msg="lrelu")
+    same_bits(lambda: (ops.activation(xc, JG_ACT_LRELU), grad_of(lambda t: ops.activation(t, JG_ACT_LRELU), xc, gy)),
+              lambda: (J.act(xc, JG_ACT_LRELU), grad_of(lambda t: J.act(t, JG_ACT_LRELU), xc, gy)), "lrelu forward, backward")
     # ---- reflect_pad2d, reflect_conv2d, dilate2d, strided conv2d_nt
     x = rnd((2, 16, 16, 64), dtype, 16).to(d).requires_grad_(True)
     w = (rnd((64, 3, 3, 64), dtype, 17).float() / 24).to(dtype).to(d).requires_grad_(True)
@@ -1969,6 +2002,7 @@ def test_torch_ops_surface_cut(dtype):
     xr = x.detach().float().cpu().requires_grad_(True)
     F.pad(xr.permute(0, 3, 1, 2), (3, 3, 3, 3), mode="reflect").backward(gp.float().cpu().permute(0, 3, 1, 2))
     cmp(xp.grad, xr.grad, msg="reflect pad")
+    same_bits(lambda: (ops.reflect_pad2d(x.detach(), 3),), lambda: (J.reflect_pad2d(x.detach(), 3),), "reflect_pad2d")
     torch.library.opcheck(J.dilate2d.default, (x, 31, 31, 2), test_utils=chk)
     xs = x.detach().clone().requires_grad_(True)
     ws = (rnd((128, 4, 4, 64), dtype, 21).float() / 32).to(dtype).to(d).requires_grad_(True)
@@ -1989,6 +2023,9 @@ def test_torch_ops_surface_cut(dtype):
     cmp(feat.grad, fr.grad, msg="gather")
     xq = rnd((32, 48), torch.float32, 25).to(d).requires_grad_(True)
     torch.library.opcheck(J.l2_normalize.default, (xq, 1e-7), test_utils=chk)
+    gq = rnd((32, 48), torch.float32, 36).to(d)
+    same_bits(lambda: (ops.l2_normalize(xq.detach(), 1e-7), grad_of(lambda t: ops.l2_normalize(t, 1e-7), xq, gq)),
+              lambda: (J.l2_normalize(xq.detach(), 1e-7)[0], grad_of(lambda t: J.l2_normalize(t, 1e-7)[0], xq, gq)), "l2_normalize forward, backward")
     for monce in (False, True):
         q = F.normalize(rnd((2 * 16, 48), torch.float32, 26), dim=1).to(d).requires_grad_(True)
         k = F.normalize(rnd((2 * 16, 48), torch.float32, 27), dim=1).to(d).requires_grad_(True)
@@ -2037,6 +2074,7 @@ def test_torch_ops_surface_cut(dtype):
     xr = xb.detach().float().cpu().requires_grad_(True)
     F.interpolate(xr.permute(0, 3, 1, 2), size=(15, 18), mode="bilinear", align_corners=False).backward(gb.float().cpu().permute(0, 3, 1, 2))
     cmp(xb.grad, xr.grad, msg="bilinear")
+    same_bits(lambda: (projected_d.bilinear(xb.detach(), 15, 18, False),), lambda: (J.bilinear2(xb.detach(), 15, 18, False),), "bilinear2")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -330,6 +330,65 @@ def test_product_does_not_import_oracle():
             "/root/reference/models", "").replace("/root/reference/", "REF/"), path
 
 
+# the launches that the module graph and the torch.ops surface share: stated once, in joligen_amd/launch.py
+_LAUNCH_LAYER = """jg_layernorm_fwd jg_layernorm_bwd jg_attn_smallkv_fwd jg_attn_smallkv_bwd2 jg_gelu_fwd jg_gelu_bwd jg_act_fwd jg_act_bwd
+jg_reflect_pad2d jg_reflect_pad2d_bwd jg_l2norm_fwd jg_l2norm_bwd jg_nce_sinkhorn_fwd jg_nce_sinkhorn_bwd jg_nce_ce jg_row_axpy jg_nce_hdce
+jg_gan_loss jg_hinge_loss jg_spectral_power_iter jg_spectral_wgrad_fix jg_bilinear2_fwd jg_bilinear2_bwd jg_linear_fwd jg_linear_bwd
+jg_ddpm_mse_loss""".split()
+# every other entry point with more than one call site, and why it is not a launch written once per surface
+_MULTI_SITE_OK = {
+    "jg_gn_stats": "BatchNorm2d of the SegFormer head and the recomputing GroupNorm backward of the functional op: different ops",
+    "jg_gn_stats_ld": "GroupNorm forward and the UNet executor's strided form: different ops",
+    "jg_gn_coef": "GroupNorm forward and the recomputing backward of the functional op",
+    "jg_gn_apply": "GroupNorm and BatchNorm2d share the apply primitive",
+    "jg_gn_bwd_reduce": "BatchNorm2d backward and the functional GroupNorm backward: different ops",
+    "jg_gn_bwd_coef": "module-graph and functional GroupNorm backward are different launch chains (statistics saved / recomputed)",
+    "jg_gn_bwd_apply": "GroupNorm (both chains) and BatchNorm2d share the apply primitive",
+    "jg_bn_coef": "SyncBatchNorm and local branch of one forward",
+    "jg_bn_bwd_coef": "SyncBatchNorm (local parameter sums, global dx sums) and local branch of one backward",
+    "jg_crop2d": "forward and adjoint mode, in ops.crop2d and in the projected discriminator's padding node",
+    "jg_scale": "DropPath, Dropout2d and the scaled branch gradient: one primitive, different ops",
+    "jg_bilinear_bwd": "resize_concat and the fallback of resize_sum: different ops",
+    "jg_layernorm_bwd_add": "LayerNorm with identity and add + LayerNorm: different nodes",
+    "jg_ddpm_p_sample": "first and later steps of one sampling loop",
+    "jg_transpose2d": "forward and backward of one node",
+    "jg_refresh_weights": "trainable and frozen descriptor table in one function",
+    "jg_last_kernel": "bench labels of the convolution and of the weight gradient",
+    "jg_get_tuning": "the tuning accessor of _lib and the JG_DETERMINISTIC query of conv2d_stats",
+}
+
+
+def test_shared_launches_are_stated_once():
+    """Both Python surfaces go through joligen_amd/launch.py: each shared C entry point has ONE textual call site, there; whatever else is
+    called from more than one place is a primitive used by different ops and is listed above with its reason."""
+    rx = re.compile(r"(lib\(\)|\bL)\.(jg_\w+)\(")
+    sites = {}
+    top = os.path.join(ROOT, "joligen_amd")
+    for dirpath, _, files in os.walk(top):
+        for f in files:
+            if f.endswith(".py"):
+                rel = os.path.relpath(os.path.join(dirpath, f), top)
+                for n, line in enumerate(open(os.path.join(dirpath, f)), 1):
+                    for m in rx.finditer(line):
+                        sites.setdefault(m.group(2), []).append(f"{rel}:{n}")
+    assert len(_LAUNCH_LAYER) == 26 and len(set(_LAUNCH_LAYER)) == 26
+    for name in _LAUNCH_LAYER:
+        where = sites.get(name, [])
+        assert len(where) == 1 and where[0].startswith("launch.py:"), (name, where)
+    multi = {k for k, v in sites.items() if len(v) > 1}
+    assert not multi & set(_LAUNCH_LAYER)
+    assert not set(_MULTI_SITE_OK) & set(_LAUNCH_LAYER)
+    assert multi - set(_MULTI_SITE_OK) == set(), {k: sites[k] for k in multi - set(_MULTI_SITE_OK)}
+    assert set(_MULTI_SITE_OK) - multi == set(), "stale allow-list entries"
+    assert all(len(reason) > 10 for reason in _MULTI_SITE_OK.values())
+    src = open(os.path.join(top, "launch.py")).read()
+    imports = re.findall(r"^\s*(?:from\s+(\S+)\s+import\s+(.+)|import\s+(.+))$", src, re.M)
+    assert imports
+    for frm, names, plain in imports:
+        text = f"{frm} {names} {plain}"
+        assert not re.search(r"\b(ops_segformer|ops_library_cut|modules|ops)\b", text), text
+
+
 def test_hot_kernels_do_not_spill(tmp_path):
     """The halo-resident convolution / weight-gradient kernels sit at the VGPR limit of their occupancy target: any scratch spill
     costs 2-3x (a reflect-padding edit once pushed the 8-row weight-gradient configuration into 95 spilled registers).  Compile
