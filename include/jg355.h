@@ -678,6 +678,28 @@ int jg_d_aug(int dtype, const void* src, int nd, const void* const* alt, const f
              uint32_t call, int B, int H, int W, int C, int Cpad, jg_stream_t s);
 int jg_apa_update(int dtype, const void* pred, int64_t n, int64_t stride, float* p, float* adjust, float* s_out, float target, float num,
                   float den, jg_stream_t s);
+/* nn.Dropout behind a normalise + activate pass (G_dropout of the ResNet generator: resnet_generator.py:62-88; D_dropout of the PatchGAN:
+ * discriminators.py:51-108), computed inside that pass and its two backward passes on 16-bit NHWC [B, H*W, C] tensors with pixel strides
+ * (C % 8 == 0, strides multiples of 8, pointers 16-byte aligned).  ab: the [B][C][2] table of jg_gn_coef, or NULL = no normalisation
+ * (a = 1, b = 0).  m[b][c][pixel] = (u < keep); the mask is never stored, every kernel regenerates it.
+ *   jg_gn_apply_drop      : y = m * act(a x + b) / keep in fp32, rounded once; a dropped element is exactly 0.
+ *   jg_gn_bwd_reduce_drop : jg_gn_bwd_reduce_ld_acc with dy * m / keep in place of dy: red [B][C][2] += (sum du, sum du x), du = (dy m / keep)
+ *                           act'(a x + b).  ab is required.  jg_gn_bwd_coef then turns red into pqr as for the plain pass.
+ *   jg_gn_bwd_apply_drop  : dx = du P + x Q + R with (P, Q, R) = pqr[b][c]; ab == NULL and pqr == NULL: dx = du = (dy m / keep) act'(x).
+ *   u: fp32 [B, C, H, W] (the reference's layout and draw), or NULL: drawn in the kernel, Philox4x32-10 on the two 32-bit words of the device
+ *   tensor `key` with the counter (pixel h * W + w, sample, stream | (c / 4) << 16, call); its four words, mapped to (0, 1) as in jg_d_aug, are
+ *   the uniforms of the channels 4 (c / 4) .. + 3.  The same (key, stream, call) give the same mask in all three kernels and on every launch.
+ *   JG_ERR_BAD_ARG: keep outside (0, 1], a draw without key, stream above 65535, act other than none / ReLU / LeakyReLU / SiLU, a bad shape,
+ *   stride or alignment (ab 16-byte aligned as the tensors are: its rows are read as 16-byte vectors), ab given without pqr or the reverse.  jg_dropout_grid_cap: the most threads (16-byte groups in flight) the two apply
+ *   passes launch; larger tensors take further trips of the grid-stride loop. */
+int jg_gn_apply_drop(int dtype, const void* x, int64_t ldx, const float* ab, void* y, int64_t ldy, int B, int H, int W, int C, int act, float keep,
+                     const float* u, const uint32_t* key, uint32_t stream, uint32_t call, jg_stream_t s);
+int jg_gn_bwd_reduce_drop(int dtype, const void* x, int64_t ldx, const void* dy, int64_t lddy, const float* ab, float* red, int B, int H, int W,
+                          int C, int act, float keep, const float* u, const uint32_t* key, uint32_t stream, uint32_t call, jg_stream_t s);
+int jg_gn_bwd_apply_drop(int dtype, const void* x, int64_t ldx, const void* dy, int64_t lddy, const float* ab, const float* pqr, void* dx,
+                         int64_t lddx, int B, int H, int W, int C, int act, float keep, const float* u, const uint32_t* key, uint32_t stream,
+                         uint32_t call, jg_stream_t s);
+int jg_dropout_grid_cap(void);
 /* dataaug_D_diffusion: Diffusion-GAN noise on the four backbone feature maps of the projected discriminator
  * (models/modules/projected_d/diffusion.py, projector.py:531-556) and the adaptive update of its strength p (models/modules/loss.py:315-331).
  * The state lives in DEVICE memory: p (fp32), Tn (int32 [2] = T, n), the tables a = sqrt(cumprod alpha) and b = sqrt(1 - cumprod alpha)

@@ -9,8 +9,7 @@
 //
 // Algorithmic bytes (T = 2 B): forward reads x twice and writes y once (6 B/elem), backward
 // reads x,dy twice and writes dx once (10 B/elem).
-#include "common.h"
-#include <cstdlib>
+#include "gn_map.h"
 
 // register budget of the two backward passes (experiment: -DJG_GN_BWD_WAVES=8 caps them at 64 VGPRs so that two of their waves fit a SIMD
 // next to a resident weight-gradient workgroup of the side stream)
@@ -21,57 +20,6 @@
 #endif
 
 namespace {
-
-struct Map {
-  int noct, pl, active, chunk;
-};
-__host__ __device__ inline Map make_map(int C) {
-  Map m;
-  m.noct = C / 8;
-  m.pl = 256 / m.noct;
-  if (m.pl < 1) m.pl = 1;
-  m.active = m.pl * m.noct;
-  m.chunk = m.pl * 16;
-  return m;
-}
-
-// reductions: 4x more pixels per block than the streaming passes (4x fewer global atomics per channel)
-__host__ __device__ inline Map make_map_red(int C, int mult) {
-  Map m = make_map(C);
-  m.chunk = m.pl * mult;   // mult in {16, 32, 64}: chosen by the host so that small tensors still fill the chip
-  return m;
-}
-inline int red_mult(int B, int HW, int C) {
-  const Map m = make_map(C);
-  // fewest workgroups a larger chunk must still leave (JG_GN_RED_MINBLK, A/B; see the statistics pass below: the closing global atomics of every
-  // workgroup weigh more than an underfilled grid on the CUT generators' maps)
-  static const int minblk = getenv("JG_GN_RED_MINBLK") ? atoi(getenv("JG_GN_RED_MINBLK")) : 2048;
-  for (int mult = 64; mult > 16; mult >>= 1)
-    if ((long)B * ((HW + m.pl * mult - 1) / (m.pl * mult)) >= minblk) return mult;
-  return 16;
-}
-
-// Deterministic forms (JG_DETERMINISTIC 1, `det`): ONE workgroup per image walks all its pixels (no cross-workgroup atomics), and the
-// threads that share a channel octet are combined by an ORDERED sum over their LDS slots instead of ds_add_f32 chains: the result does not
-// depend on the order in which waves and workgroups happen to run.  s_part: 256 threads x 16 partial sums behind the [C][2] row.
-__device__ __forceinline__ void ordered_octet_sum(float* s_acc, const float (&s1)[8], const float (&s2)[8], const Map& mp, int C, bool active) {
-  float* s_part = s_acc + 2 * C;
-  const int tid = threadIdx.x;
-  if (active) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      s_part[tid * 16 + q * 2] = s1[q];
-      s_part[tid * 16 + q * 2 + 1] = s2[q];
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < 2 * C; i += 256) {
-    const int c = i >> 1, k = i & 1, co = c >> 3, q = c & 7;
-    float s = 0.f;
-    for (int pl = 0; pl < mp.pl; ++pl) s += s_part[(pl * mp.noct + co) * 16 + q * 2 + k];
-    s_acc[i] = s;
-  }
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, long ldx, float* __restrict__ sums, long ldsums,
@@ -556,8 +504,6 @@ __global__ JG_GN_BWD_BOUNDS void gn_bwd_apply_kernel(const T* __restrict__ x, lo
         add2 ? *reinterpret_cast<const uint4*>(add2 + (row0 + p) * ldadd2 + co * 8) : make_uint4(0, 0, 0, 0), p);
   }
 }
-
-inline bool bad_shape(int B, int HW, int C) { return B < 1 || HW < 1 || C < 8 || (C % 8) || C > 2048 || B > 65535; }
 
 }  // namespace
 

@@ -1,4 +1,4 @@
-// Counter-based random numbers of the augmentation kernels (d_aug.hip, d_diffusion.hip): Philox4x32-10 (Salmon et al., "Parallel random
+// Counter-based random numbers of the augmentation and dropout kernels (d_aug.hip, d_diffusion.hip, dropout.hip): Philox4x32-10 (Salmon et al., "Parallel random
 // numbers: as easy as 1, 2, 3", SC'11), the map of a word to the open unit interval, and Box-Muller in fp32.
 //   uniform u = ((x >> 9) + 0.5) * 2^-23: 2^23 values, every one exact in fp32, inside the OPEN interval (0, 1): log(u) is finite
 //   normals   r = sqrt(-2 log(u0)), t = 2 pi u1: (r cos t, r sin t), all in fp32

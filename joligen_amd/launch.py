@@ -177,6 +177,33 @@ def act_bwd(y, dy, kind):
     return dx
 
 
+# ---- nn.Dropout inside the normalise + activate passes (csrc/dropout.hip) ----------------------------------------------------------------
+def gn_apply_drop(x, ab, act, keep, u, key, stream, call):
+    """y = m * act(a x + b) / keep on x [B, H, W, C] with m = (u < keep); ab [B, C, 2] or None (no normalisation); u fp32 [B, C, H, W] or None:
+    drawn in the kernel from the two words of `key` on the counter (pixel, b, stream | (c / 4) << 16, call)"""
+    B, H, W, C = x.shape
+    y = torch.empty_like(x)
+    check(_lib.lib().jg_gn_apply_drop(_dt(x), x.data_ptr(), C, _p(ab), y.data_ptr(), C, B, H, W, C, act, keep, _p(u), _p(key), stream, call, _st()),
+          "jg_gn_apply_drop")
+    return y
+
+
+def gn_bwd_reduce_drop(x, dy, ab, red, act, keep, u, key, stream, call):
+    """red [B, C, 2] += (sum du, sum du x) with du = (dy m / keep) act'(a x + b): the mask of gn_apply_drop, regenerated"""
+    B, H, W, C = x.shape
+    check(_lib.lib().jg_gn_bwd_reduce_drop(_dt(x), x.data_ptr(), C, dy.data_ptr(), C, ab.data_ptr(), red.data_ptr(), B, H, W, C, act, keep, _p(u),
+                                           _p(key), stream, call, _st()), "jg_gn_bwd_reduce_drop")
+
+
+def gn_bwd_apply_drop(x, dy, ab, pqr, act, keep, u, key, stream, call):
+    """-> dx = du P + x Q + R (ab, pqr None: dx = du = (dy m / keep) act'(x))"""
+    B, H, W, C = x.shape
+    dx = torch.empty_like(x)
+    check(_lib.lib().jg_gn_bwd_apply_drop(_dt(x), x.data_ptr(), C, dy.data_ptr(), C, _p(ab), _p(pqr), dx.data_ptr(), C, B, H, W, C, act, keep, _p(u),
+                                          _p(key), stream, call, _st()), "jg_gn_bwd_apply_drop")
+    return dx
+
+
 # ---- reflection padding, bilinear resize -----------------------------------------------------------------------------------------------
 def reflect_pad2d(x, pad):
     B, H, W, C = x.shape

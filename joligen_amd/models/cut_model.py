@@ -22,6 +22,7 @@ from .. import ops
 from ..modules.NCE.hdce import PatchHDCELoss
 from ..modules.NCE.patchnce import MoNCELoss, PatchNCELoss
 from ..modules.cut_networks import PatchSampleF
+from ..modules.dropout import DropoutState, FusedDropout, bind_dropout
 from ..modules.resnet_generator import ResnetGenerator
 from ..options import D_AUG_DEFAULTS, SEM_CLS_DEFAULTS
 from ..util.image_pool import ImagePool
@@ -97,6 +98,28 @@ def check_d_aug_options(opt):
         if len(opt.D_netDs) > ops.D_AUG_MAX:
             raise NotImplementedError(f"dataaug_APA with more than {ops.D_AUG_MAX} discriminators")
     return sigma, apa
+
+
+DROPOUT_GENERATORS = ("resnet", "resnet_9blocks", "resnet_6blocks")      # gan_networks.py:112-122: the only G_netG that receive G_dropout
+
+
+def check_dropout_options(opt):
+    """G_dropout / D_dropout (nn.Dropout(0.5) in every ResnetBlock: resnet_generator.py:62-88; behind every LeakyReLU of the PatchGAN:
+    discriminators.py:51-108) as this build accepts them; returns (generator dropout, PatchGAN dropout).  The reference hands G_dropout to the
+    plain ResNet generator only: for every other G_netG it is ignored there and, with a warning, here.  projected_d has no dropout in the
+    reference: D_dropout reaches the 'basic' discriminator only.  The value of G_dropout is not a rate: the networks use 0.5.  Host-only
+    (no device)."""
+    for k in ("G_dropout", "D_dropout", "D_netDs"):
+        if not hasattr(opt, k):
+            setattr(opt, k, CUT_DEFAULTS.get(k, False))
+    g, d = bool(opt.G_dropout), bool(opt.D_dropout)
+    if g and getattr(opt, "G_netG", "resnet") not in DROPOUT_GENERATORS:
+        warnings.warn(f"G_dropout has no effect: G_netG={opt.G_netG!r} is not handed it (only {DROPOUT_GENERATORS} are, as in the reference)")
+        g = False
+    if d and "basic" not in opt.D_netDs:
+        warnings.warn(f"D_dropout has no effect: D_netDs={opt.D_netDs!r} holds no 'basic' discriminator")
+        d = False
+    return g, d
 
 
 SEM_CLS_MODES = {"CE": ops.CLS_CE, "MSE": ops.CLS_MSE, "L1": ops.CLS_L1}      # check_sem_cls_options -> mode of ops.cls_loss
@@ -192,9 +215,9 @@ class CUTModel(BaseModel):
         # cut_model.py:752-766: with alg_cut_MSE_idt the identity contrastive term of SRC_hDCE runs with the hDCE weights too
         self.hdce_idt_weighted = bool(self.hdce and opt.alg_cut_MSE_idt)
         # options that select ANOTHER network than the one built here must not be dropped silently: the generator /
-        # PatchGAN below are the InstanceNorm, no-dropout, no-spectral-norm variants of gan_networks.define_G / define_D
-        for name, built in (("G_dropout", False), ("D_dropout", False), ("D_spectral", False), ("G_spectral", False),
-                            ("G_norm", "instance"), ("D_norm", "instance")):
+        # PatchGAN below are the InstanceNorm, no-spectral-norm variants of gan_networks.define_G / define_D
+        self.g_dropout, self.d_dropout = check_dropout_options(opt)
+        for name, built in (("D_spectral", False), ("G_spectral", False), ("G_norm", "instance"), ("D_norm", "instance")):
             val = getattr(opt, name, built)
             if val != built and not (name.endswith("_norm") and "segformer" in opt.G_netG and name == "G_norm"):
                 raise NotImplementedError(f"{name}={val!r}: only {built!r} is built for the CUT networks")
@@ -217,7 +240,7 @@ class CUTModel(BaseModel):
                                                twice_resnet_blocks=getattr(opt, "G_backward_compatibility_twice_resnet_blocks", False))
         else:
             self.netG_A = ResnetGenerator(opt.model_input_nc, opt.model_output_nc, opt.G_ngf, n_blocks=opt.G_nblocks,
-                                          padding_type=opt.G_padding_type)
+                                          padding_type=opt.G_padding_type, use_dropout=self.g_dropout)
         self.model_names = ["G_A"]
         if opt.isTrain:
             self.netF = PatchSampleF(use_mlp=True, init_type=opt.model_init_type, init_gain=opt.model_init_gain, nc=opt.alg_cut_netF_nc)
@@ -259,6 +282,39 @@ class CUTModel(BaseModel):
         self.d_noise, self.d_apa = check_d_aug_options(opt)
         if self.d_apa and opt.isTrain:
             self.visual_names.append(["APA_img"])
+        self._bind_dropout()
+
+    # ---- G_dropout / D_dropout ------------------------------------------------------------------------------------------------------------
+    def _bind_dropout(self):
+        """One DropoutState for the generator and every discriminator: unique Philox streams across them, module paths `netG_A.encoder...` /
+        `netD_B_basic.model...`, ONE key per step.  The key lives in a buffer of the model's own that the step refills in place
+        (`_forward_core`, inside the captured region), so that the generator graphs and the discriminator graph read the same address."""
+        self.dropout_state = DropoutState()
+        nets = [("netG_A", self.netG_A)] + [("net" + dn, getattr(self, "net" + dn)) for dn in getattr(self, "discriminators_names", [])]
+        n = 0
+        for name, net in nets:
+            if hasattr(net, "dropout_state"):
+                n = bind_dropout(net, self.dropout_state, name + ".", n)
+        self._dropout_on = n > 0
+        self._drop_key = torch.zeros(2, device=self.device, dtype=torch.int32) if self._dropout_on else None
+
+    @property
+    def dropout_rand(self):
+        """parity runs: callable(module_path, call, shape_BCHW, device) -> the fp32 uniforms of that invocation of that Dropout module"""
+        return self.dropout_state.rand
+
+    @dropout_rand.setter
+    def dropout_rand(self, fn):
+        self.dropout_state.rand = fn
+
+    def _dropout_seek(self, names, call):
+        """the next invocation of every Dropout module of the networks `names` is `call`: the discriminators run once in the generator's loss
+        (call 0) and then in their own half (from call 1), whichever driver enqueues the halves and whether or not a half is replayed"""
+        if self._dropout_on:
+            for nm in names:
+                for m in self._net(nm).modules():
+                    if isinstance(m, FusedDropout):
+                        self.dropout_state.calls[m.stream] = call
 
     # ---- semantic-consistency class branch (train_semantic_cls) -------------------------------------------------------------------------
     def init_semantic_cls(self, opt, kw):
@@ -390,6 +446,12 @@ class CUTModel(BaseModel):
         B = self.batch_size
         self.real = torch.cat((self.real_A, self.real_B), dim=0) if self.opt.alg_cut_nce_idt else self.real_A
         self._real_feats = None
+        if self._dropout_on and self.opt.isTrain:
+            # a new step for every Dropout module: invocation counts back to 0 and one fresh Philox key, drawn on the device into the model's
+            # own buffer (inside the generator graph when the step is captured, as the key of dataaug_D_noise is inside its region)
+            if self.dropout_state.rand is None:
+                self._drop_key.copy_(ops.d_aug_key(self.device))
+            self.dropout_state.begin_step(self._drop_key)
         if self._reuse_feats():
             self.fake, self._real_feats = self._net("G_A").forward_with_feats(self.real, self.nce_layers)
         else:
@@ -435,6 +497,7 @@ class CUTModel(BaseModel):
 
     def compute_G_loss_GAN(self):
         """base_gan_model.py:421-503: lambda_GAN * compute_loss_G of every discriminator on domain B."""
+        self._dropout_seek(self.discriminators_names, 0)
         for dn in self.discriminators_names:
             lossf = getattr(self, dn + "_loss_calculator")
             val = self.opt.alg_gan_lambda * lossf.compute_loss_G(self._net(dn), self.real_B, self.fake_B)
@@ -446,6 +509,8 @@ class CUTModel(BaseModel):
         identity term, an un-injected random source (parity runs inject per-call draws in the reference's order) and the per-image negatives"""
         o = self.opt
         net = self._net("G_A")
+        if self.g_dropout:      # the reference draws a fresh mask in each of its four encoder passes: the same passes, the same (stream, call) pairs
+            return False
         return (gate(o, "jg_batched_nce", "JG_BATCHED_NCE") and o.alg_cut_nce_idt and o.alg_cut_lambda_NCE > 0.0
                 and self.patch_ids_injection is None and getattr(getattr(net, "rand", None), "source", None) is None
                 and not o.alg_cut_nce_includes_all_negatives_from_minibatch and not ops.TORCH_OPS_BOUNDARY)
@@ -641,6 +706,7 @@ class CUTModel(BaseModel):
         drawn = self.driver.drawn_fakes          # early-D driver: drawn before the fork (same draw order)
         fakes, alts = drawn if drawn is not None else self.draw_D_fakes()
         reals = self.real_D_operands(alts)
+        self._dropout_seek(self.discriminators_names, 1)
         for i, dn in enumerate(self.discriminators_names):
             val = getattr(self, dn + "_loss_calculator").compute_loss_D(self._net(dn), reals[i], fakes[i], None)
             setattr(self, "loss_D_GAN_" + dn, val)
@@ -650,6 +716,7 @@ class CUTModel(BaseModel):
     def _d_half_body(self, reals, fakes, its):
         """compute_D_loss + backward on given operands (the pool draws and the augmentations are the caller's)"""
         vals, tot = [], 0
+        self._dropout_seek(self.discriminators_names, 1)
         for dn, real, fake in zip(self.discriminators_names, reals, fakes):
             val = getattr(self, dn + "_loss_calculator").compute_loss_D(self._net(dn), real, fake, None)
             vals.append(val)

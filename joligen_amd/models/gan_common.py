@@ -52,7 +52,8 @@ def define_discriminators(model, opt):
     names = []
     for d in opt.D_netDs:
         if d == "basic":
-            net = NLayerDiscriminator(opt.model_output_nc, opt.D_ndf, n_layers=opt.D_n_layers)
+            # D_dropout reaches the PatchGAN only (cut_model.check_dropout_options; cm_gan refuses it)
+            net = NLayerDiscriminator(opt.model_output_nc, opt.D_ndf, n_layers=opt.D_n_layers, use_dropout=bool(getattr(opt, "D_dropout", False)))
         else:
             from ..modules.projected_d import ProjectedDiscriminator
 

@@ -689,8 +689,26 @@ def zeros_f32(n, device):
     return out
 
 
-def _group_norm_launch(x, gamma, beta, film, G, act, eps, sums=None, add=None):
-    """the GroupNorm forward chain: statistics (unless given), coefficients, apply (+ add) -> (y, ab [B, C, 2], mr [B, G, 2])"""
+def _drop_args(x, keep, u, key, stream, call):
+    """the checked dropout arguments (keep, u, key, stream, call) of the fused passes of csrc/dropout.hip: u fp32 [B, C, H, W] injected uniforms
+    or None = drawn in the kernel from the two-word device tensor `key` (d_aug_key)"""
+    keep, stream, call = float(keep), int(stream), int(call)
+    if x.dim() != 4 or not 0.0 < keep <= 1.0 or not 0 <= stream < 65536 or not 0 <= call < 2 ** 32:
+        raise ValueError(f"dropout: x [B, H, W, C], keep in (0, 1], stream < 65536 (got {tuple(x.shape)}, keep={keep}, stream={stream}, call={call})")
+    B, H, W, C = x.shape
+    if u is not None:
+        if u.dtype != torch.float32 or tuple(u.shape) != (B, C, H, W):
+            raise ValueError(f"dropout: u must be fp32 [B, C, H, W] = {(B, C, H, W)}, got {u.dtype} {tuple(u.shape)}")
+        u, key = u.contiguous(), None
+    elif key is None or key.numel() != 2 or key.element_size() != 4:
+        raise ValueError("dropout: a draw needs the two-word Philox key (ops.d_aug_key)")
+    _require_cuda(x, u, key)
+    return keep, u, key, stream, call
+
+
+def _group_norm_launch(x, gamma, beta, film, G, act, eps, sums=None, add=None, drop=None):
+    """the GroupNorm forward chain: statistics (unless given), coefficients, apply (+ add) -> (y, ab [B, C, 2], mr [B, G, 2]);
+    drop = (keep, u, key, stream, call): nn.Dropout behind the activation, inside the apply pass"""
     _require_cuda(x)
     L = _lib.lib()
     B, C = x.shape[0], x.shape[-1]
@@ -698,13 +716,15 @@ def _group_norm_launch(x, gamma, beta, film, G, act, eps, sums=None, add=None):
     dev, st, dt = x.device, _st(), _dt(x)
     ab = torch.empty((B, C, 2), device=dev, dtype=torch.float32)
     mr = torch.empty((B, G, 2), device=dev, dtype=torch.float32)
-    y = torch.empty_like(x)
     ldfilm = film.stride(0) if film is not None else 0
     if sums is None:            # (given: the producing convolution's epilogue has accumulated them, ops.conv2d_stats)
         sums = zeros_f32(B * C * 2, dev)[:B * C * 2].view(B, C, 2)
         check(L.jg_gn_stats_ld(dt, x.data_ptr(), C, sums.data_ptr(), C, B, HW, C, st), "jg_gn_stats_ld")
     check(L.jg_gn_coef(sums.data_ptr(), _p(gamma), _p(beta), _p(film), ldfilm, ab.data_ptr(), mr.data_ptr(), B, HW, C,
                        G, eps, st), "jg_gn_coef")
+    if drop is not None:
+        return launch.gn_apply_drop(x, ab, act, *drop), ab, mr
+    y = torch.empty_like(x)
     if add is not None:          # y = act(norm(x)) + add in the apply pass (round 6); d(add) = dy
         add = add.contiguous()
         check(L.jg_gn_apply_add(dt, x.data_ptr(), C, ab.data_ptr(), add.data_ptr(), C, y.data_ptr(), C, B, HW, C, act, st), "jg_gn_apply_add")
@@ -751,6 +771,77 @@ class _GroupNormFn(JGFunction):
         return dx, None, None, dfilm, None, None, None, None, (dy if ctx.needs_input_grad[8] else None)
 
 
+def _gn_drop_bwd_launch(x, dy, ab, mr, gamma, beta, film, G, act, drop, red, dgamma, dbeta, dfilm, want_dx=True):
+    """the GroupNorm backward chain behind a fused dropout: reduce (mask regenerated) -> coefficients -> apply (mask regenerated); `red` is
+    zeroed [B, C, 2]; dgamma / dbeta are accumulated into, dfilm is written (None: not wanted) -> dx"""
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    pqr = torch.empty((B, C, 3), device=x.device, dtype=torch.float32)
+    ldfilm = film.stride(0) if film is not None else 0
+    launch.gn_bwd_reduce_drop(x, dy, ab, red, act, *drop)
+    check(_lib.lib().jg_gn_bwd_coef(red.data_ptr(), _p(gamma), _p(beta), _p(film), ldfilm, mr.data_ptr(), pqr.data_ptr(), _p(dgamma), _p(dbeta),
+                                    _p(dfilm), 2 * C, B, HW, C, G, _st()), "jg_gn_bwd_coef")
+    return launch.gn_bwd_apply_drop(x, dy, ab, pqr, act, *drop) if want_dx else None
+
+
+class _GroupNormDropFn(JGFunction):
+    """_GroupNormFn with nn.Dropout behind the activation: y = m * act(norm(x)) / keep.  The mask is not saved: the backward passes
+    regenerate it from (u | key, stream, call)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, film, G, act, eps, sums, keep, u, key, stream, call):
+        x = x.contiguous()
+        drop = _drop_args(x, keep, u, key, stream, call)
+        y, ab, mr = _group_norm_launch(x, gamma, beta, film, G, act, eps, sums, None, drop)
+        ctx.save_for_backward(x, ab, mr, gamma, beta, film, drop[1], drop[2])
+        ctx.G, ctx.act, ctx.drop = G, act, (drop[0], drop[3], drop[4])
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, ab, mr, gamma, beta, film, u, key = ctx.saved_tensors
+        keep, stream, call = ctx.drop
+        B, C = x.shape[0], x.shape[-1]
+        red = zeros_f32(B * C * 2, x.device)[:B * C * 2].view(B, C, 2)
+        want_film = film is not None and ctx.needs_input_grad[3]
+        dfilm = torch.empty((B, 2 * C), device=x.device, dtype=torch.float32) if want_film else None
+        dgamma = gamma.grad if (gamma is not None and ctx.needs_input_grad[1]) else None
+        dbeta = beta.grad if (beta is not None and ctx.needs_input_grad[2]) else None
+        if (gamma is not None and ctx.needs_input_grad[1] and dgamma is None):
+            raise RuntimeError("norm weight has no arena-backed .grad")
+        dx = _gn_drop_bwd_launch(x, dy.contiguous(), ab, mr, gamma, beta, film, ctx.G, ctx.act, (keep, u, key, stream, call), red, dgamma, dbeta,
+                                 dfilm, ctx.needs_input_grad[0])
+        return (dx, None, None, dfilm) + (None,) * 9
+
+
+class _ActDropFn(JGFunction):
+    """m * act(x) / keep where no normalisation precedes the activation (the PatchGAN's first layer); the backward reads x, not y: a dropped
+    element of y says nothing about the sign of x"""
+
+    @staticmethod
+    def forward(ctx, x, act, keep, u, key, stream, call):
+        x = x.contiguous()
+        drop = _drop_args(x, keep, u, key, stream, call)
+        ctx.save_for_backward(x, drop[1], drop[2])
+        ctx.act, ctx.drop = act, (drop[0], drop[3], drop[4])
+        return launch.gn_apply_drop(x, None, act, *drop)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, u, key = ctx.saved_tensors
+        keep, stream, call = ctx.drop
+        return (launch.gn_bwd_apply_drop(x, dy.contiguous(), None, None, ctx.act, keep, u, key, stream, call),) + (None,) * 6
+
+
+def activation_dropout(x, act, keep, u=None, key=None, stream=0, call=0):
+    """nn.Dropout(1 - keep)(act(x)) in one pass on x [B, H, W, C] (act: JG_ACT_NONE / RELU / LRELU / SILU); the arguments as in group_norm"""
+    if TORCH_OPS_BOUNDARY:
+        return torch.ops.jg355.act_drop(x, act, float(keep), u, key, int(stream), int(call))
+    return _ActDropFn.apply(x, act, keep, u, key, stream, call)
+
+
 _GN_STATUS = {}
 
 
@@ -770,9 +861,20 @@ def check_gn_status():
             raise RuntimeError(f"jg_gn_bwd_fused: an inter-workgroup wait expired on cuda:{k} (results of that launch are invalid)")
 
 
-def group_norm(x, G, gamma=None, beta=None, film=None, act=JG_ACT_NONE, eps=1e-5, sums=None, add=None):
+def group_norm(x, G, gamma=None, beta=None, film=None, act=JG_ACT_NONE, eps=1e-5, sums=None, add=None, keep=None, u=None, key=None, stream=0,
+               call=0):
     """act(GroupNorm_G(x) * gamma + beta [* (1 + scale) + shift]); statistics in fp32.  sums: the [B, C, 2] statistics of x where a
-    convolution's epilogue has already taken them (conv2d_stats)."""
+    convolution's epilogue has already taken them (conv2d_stats).
+    keep (None: no dropout, the launches are those of before): nn.Dropout(1 - keep) behind the activation in the same pass, x [B, H, W, C];
+    u: injected uniforms fp32 [B, C, H, W], else the mask is drawn in the kernel from `key` (d_aug_key), `stream` (< 65536, the Dropout
+    module) and `call` (its invocation within the step).  Under TORCH_OPS_BOUNDARY the functional ops take their own statistics, with or
+    without dropout: `sums` is not used there."""
+    if keep is not None:
+        if add is not None:
+            raise ValueError("group_norm: dropout and a residual addend do not occur behind one normalisation")
+        if TORCH_OPS_BOUNDARY:
+            return torch.ops.jg355.group_norm_act_drop(x, gamma, beta, film, G, act, eps, float(keep), u, key, int(stream), int(call))
+        return _GroupNormDropFn.apply(x, gamma, beta, film, G, act, eps, sums, keep, u, key, stream, call)
     if TORCH_OPS_BOUNDARY:
         y = torch.ops.jg355.group_norm_act(x, gamma, beta, film, G, act, eps)
         return y if add is None else y + add
@@ -2259,6 +2361,110 @@ def _gn_backward(ctx, dy):
 
 
 _op_group_norm_act.register_autograd(_gn_backward, setup_context=_gn_setup)
+
+
+@torch.library.custom_op("jg355::group_norm_act_drop", mutates_args=())
+def _op_group_norm_act_drop(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], film: Optional[torch.Tensor],
+                            groups: int, act: int, eps: float, keep: float, u: Optional[torch.Tensor], key: Optional[torch.Tensor], stream: int,
+                            call: int) -> torch.Tensor:
+    """group_norm_act with nn.Dropout(1 - keep) behind the activation in the apply pass: x [B, H, W, C]; u fp32 [B, C, H, W] or None = drawn
+    in the kernel from the two-word `key`, `stream` and `call`"""
+    x = x.contiguous()
+    return _group_norm_launch(x, gamma, beta, None if film is None else film.contiguous(), groups, act, eps, None, None,
+                              _drop_args(x, keep, u, key, stream, call))[0]
+
+
+@_op_group_norm_act_drop.register_fake
+def _(x, gamma, beta, film, groups, act, eps, keep, u, key, stream, call):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("jg355::group_norm_act_drop_bwd", mutates_args=())
+def _op_group_norm_act_drop_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor],
+                                film: Optional[torch.Tensor], groups: int, act: int, eps: float, keep: float, u: Optional[torch.Tensor],
+                                key: Optional[torch.Tensor], stream: int, call: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dgamma [C], dbeta [C], dfilm [B, 2C]) -- the statistics are recomputed from x, the mask is regenerated"""
+    L = _lib.lib()
+    x, dy = x.contiguous(), dy.contiguous()
+    drop = _drop_args(x, keep, u, key, stream, call)
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * C)
+    f32 = dict(device=x.device, dtype=torch.float32)
+    sums, ab, mr = torch.empty((B, C, 2), **f32), torch.empty((B, C, 2), **f32), torch.empty((B, groups, 2), **f32)
+    film = None if film is None else film.contiguous()
+    ldfilm = film.stride(0) if film is not None else 0
+    check(L.jg_gn_stats(_dt(x), x.data_ptr(), sums.data_ptr(), B, HW, C, _st()), "jg_gn_stats")
+    check(L.jg_gn_coef(sums.data_ptr(), _p(gamma), _p(beta), _p(film), ldfilm, ab.data_ptr(), mr.data_ptr(), B, HW, C, groups, eps, _st()), "jg_gn_coef")
+    dgamma, dbeta, dfilm = torch.zeros((C,), **f32), torch.zeros((C,), **f32), torch.zeros((B, 2 * C), **f32)
+    dx = _gn_drop_bwd_launch(x, dy, ab, mr, gamma, beta, film, groups, act, drop, torch.zeros((B, C, 2), **f32), dgamma if gamma is not None else None,
+                             dbeta if beta is not None else None, dfilm if film is not None else None)
+    return dx, dgamma, dbeta, dfilm
+
+
+@_op_group_norm_act_drop_bwd.register_fake
+def _(x, dy, gamma, beta, film, groups, act, eps, keep, u, key, stream, call):
+    B, C = x.shape[0], x.shape[-1]
+    f = lambda *sh: x.new_empty(sh, dtype=torch.float32)
+    return torch.empty_like(x, memory_format=torch.contiguous_format), f(C), f(C), f(B, 2 * C)
+
+
+def _gnd_setup(ctx, inputs, output):
+    x, gamma, beta, film, groups, act, eps, keep, u, key, stream, call = inputs
+    ctx.save_for_backward(x, gamma, beta, film, u, key)
+    ctx.cfg = (groups, act, eps, keep, stream, call)
+
+
+def _gnd_backward(ctx, dy):
+    x, gamma, beta, film, u, key = ctx.saved_tensors
+    groups, act, eps, keep, stream, call = ctx.cfg
+    dx, dgamma, dbeta, dfilm = torch.ops.jg355.group_norm_act_drop_bwd(x, dy, gamma, beta, film, groups, act, eps, keep, u, key, stream, call)
+    return (dx if ctx.needs_input_grad[0] else None, dgamma if (gamma is not None and ctx.needs_input_grad[1]) else None,
+            dbeta if (beta is not None and ctx.needs_input_grad[2]) else None,
+            dfilm if (film is not None and ctx.needs_input_grad[3]) else None) + (None,) * 8
+
+
+_op_group_norm_act_drop.register_autograd(_gnd_backward, setup_context=_gnd_setup)
+
+
+@torch.library.custom_op("jg355::act_drop", mutates_args=())
+def _op_act_drop(x: torch.Tensor, act: int, keep: float, u: Optional[torch.Tensor], key: Optional[torch.Tensor], stream: int,
+                 call: int) -> torch.Tensor:
+    """nn.Dropout(1 - keep)(act(x)) in one pass, no normalisation in front: x [B, H, W, C]"""
+    x = x.contiguous()
+    return launch.gn_apply_drop(x, None, act, *_drop_args(x, keep, u, key, stream, call))
+
+
+@_op_act_drop.register_fake
+def _(x, act, keep, u, key, stream, call):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("jg355::act_drop_bwd", mutates_args=())
+def _op_act_drop_bwd(x: torch.Tensor, dy: torch.Tensor, act: int, keep: float, u: Optional[torch.Tensor], key: Optional[torch.Tensor], stream: int,
+                     call: int) -> torch.Tensor:
+    """dx = (dy m / keep) act'(x), the mask regenerated"""
+    x = x.contiguous()
+    return launch.gn_bwd_apply_drop(x, dy.contiguous(), None, None, act, *_drop_args(x, keep, u, key, stream, call))
+
+
+@_op_act_drop_bwd.register_fake
+def _(x, dy, act, keep, u, key, stream, call):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+def _ad_setup(ctx, inputs, output):
+    x, act, keep, u, key, stream, call = inputs
+    ctx.save_for_backward(x, u, key)
+    ctx.cfg = (act, keep, stream, call)
+
+
+def _ad_backward(ctx, dy):
+    x, u, key = ctx.saved_tensors
+    act, keep, stream, call = ctx.cfg
+    return (torch.ops.jg355.act_drop_bwd(x, dy, act, keep, u, key, stream, call),) + (None,) * 6
+
+
+_op_act_drop.register_autograd(_ad_backward, setup_context=_ad_setup)
 
 
 @torch.library.custom_op("jg355::attention_core", mutates_args=())

@@ -21,9 +21,10 @@ import torch.nn.functional as F
 
 
 class _ResnetBlock(nn.Module):
-    def __init__(self, dim):
+    def __init__(self, dim, use_dropout=False):
         super().__init__()
         self.conv_block = nn.Sequential(nn.ReflectionPad2d(1), nn.Conv2d(dim, dim, 3), nn.InstanceNorm2d(dim), nn.ReLU(True),
+                                        *([nn.Dropout(0.5)] if use_dropout else []),      # G_dropout: the later keys move up by one
                                         nn.ReflectionPad2d(1), nn.Conv2d(dim, dim, 3), nn.InstanceNorm2d(dim))
 
     def forward(self, x):
@@ -42,14 +43,14 @@ class _Seq(nn.Module):
 
 
 class TorchResnetGenerator(nn.Module):
-    """ResnetGenerator = ResnetEncoder + ResnetDecoder, InstanceNorm, reflect padding, no dropout (the configuration CUTModel builds)"""
+    """ResnetGenerator = ResnetEncoder + ResnetDecoder, InstanceNorm, reflect padding (the configuration CUTModel builds)"""
 
-    def __init__(self, input_nc, output_nc, ngf=64, n_blocks=9):
+    def __init__(self, input_nc, output_nc, ngf=64, n_blocks=9, use_dropout=False):
         super().__init__()
         enc = [nn.ReflectionPad2d(3), nn.Conv2d(input_nc, ngf, 7), nn.InstanceNorm2d(ngf), nn.ReLU(True),
                nn.Conv2d(ngf, ngf * 2, 3, stride=2, padding=1), nn.InstanceNorm2d(ngf * 2), nn.ReLU(True),
                nn.Conv2d(ngf * 2, ngf * 4, 3, stride=2, padding=1), nn.InstanceNorm2d(ngf * 4), nn.ReLU(True)]
-        enc += [_ResnetBlock(ngf * 4) for _ in range(n_blocks)]
+        enc += [_ResnetBlock(ngf * 4, use_dropout) for _ in range(n_blocks)]
         dec = [nn.ConvTranspose2d(ngf * 4, ngf * 2, 3, stride=2, padding=1, output_padding=1), nn.InstanceNorm2d(ngf * 2), nn.ReLU(True),
                nn.ConvTranspose2d(ngf * 2, ngf, 3, stride=2, padding=1, output_padding=1), nn.InstanceNorm2d(ngf), nn.ReLU(True),
                nn.ReflectionPad2d(3), nn.Conv2d(ngf, output_nc, 7), nn.Tanh()]
@@ -125,7 +126,7 @@ def define_torch_G(opt):
     """plain-torch generator with the reference's state_dict keys for opt.G_netG, or None when no mirror exists"""
     g = opt.G_netG
     if g in ("resnet", "resnet_9blocks", "resnet_6blocks"):
-        return TorchResnetGenerator(opt.model_input_nc, opt.model_output_nc, opt.G_ngf, opt.G_nblocks)
+        return TorchResnetGenerator(opt.model_input_nc, opt.model_output_nc, opt.G_ngf, opt.G_nblocks, use_dropout=bool(getattr(opt, "G_dropout", False)))
     if g in ("resnet_attn", "mobile_resnet_attn"):
         return TorchResnetGeneratorAttn(opt.model_input_nc, opt.model_output_nc, getattr(opt, "G_attn_nb_mask_attn", 10),
                                         getattr(opt, "G_attn_nb_mask_input", 1), opt.G_ngf, opt.G_nblocks, mobile=g.startswith("mobile"),
