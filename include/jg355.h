@@ -700,6 +700,18 @@ int jg_gn_bwd_apply_drop(int dtype, const void* x, int64_t ldx, const void* dy, 
                          int64_t lddx, int B, int H, int W, int C, int act, float keep, const float* u, const uint32_t* key, uint32_t stream,
                          uint32_t call, jg_stream_t s);
 int jg_dropout_grid_cap(void);
+/* The same dropout behind a GroupNorm that runs in FRONT of a nearest 2x upsample (the up-blocks of the efficient diffusion UNet,
+ * unet_generator_attn.py:207-242: normalise at the low resolution, mask at the high one).  x / g are [B, H, W, C], y / dy [B, 2H, 2W, C].
+ *   jg_gn_apply_drop_up2 : y[b,i,j,c] = m[b,c,i,j] * act(a x[b,i/2,j/2,c] + b) / keep in fp32, rounded once; a dropped element is exactly 0.  Bit
+ *                          for bit what jg_gn_apply_drop gives on the materialised upsample of x with the same (key, stream, call) or u.
+ *   jg_drop_pool2_bwd    : g[b,i,j,c] = sum over the 2 x 2 cell of dy * m / keep, summed in fp32 and rounded once: the adjoint of mask + upsample;
+ *                          the plain GroupNorm backward then runs on g at the low resolution.
+ *   The counter is that of jg_gn_apply_drop at the high resolution (pixel = i * 2W + j); u is fp32 [B, C, 2H, 2W].  Arguments are checked as
+ *   for the three passes above (4 H W has to fit 31 bits). */
+int jg_gn_apply_drop_up2(int dtype, const void* x, int64_t ldx, const float* ab, void* y, int64_t ldy, int B, int H, int W, int C, int act,
+                         float keep, const float* u, const uint32_t* key, uint32_t stream, uint32_t call, jg_stream_t s);
+int jg_drop_pool2_bwd(int dtype, const void* dy, int64_t lddy, void* g, int64_t ldg, int B, int H, int W, int C, float keep, const float* u,
+                      const uint32_t* key, uint32_t stream, uint32_t call, jg_stream_t s);
 /* dataaug_D_diffusion: Diffusion-GAN noise on the four backbone feature maps of the projected discriminator
  * (models/modules/projected_d/diffusion.py, projector.py:531-556) and the adaptive update of its strength p (models/modules/loss.py:315-331).
  * The state lives in DEVICE memory: p (fp32), Tn (int32 [2] = T, n), the tables a = sqrt(cumprod alpha) and b = sqrt(1 - cumprod alpha)

@@ -9,6 +9,12 @@
 //   (pixel h * W + w,  sample b,  stream | (c / 4) << 16,  call)
 // whose four words map to the uniforms of the channels 4 (c / 4) .. + 3.  `stream` names the Dropout module, `call` its invocation within the
 // step.  A thread owns one 16-byte group of 8 channels of one pixel: two Philox calls per group.
+//
+// Behind a GroupNorm that runs in front of a nearest 2x upsample (the up-blocks of the efficient diffusion UNet) the mask lives at the HIGH resolution:
+//   jg_gn_apply_drop_up2  y[b, i, j, c] = m[b, c, i, j] * act(a x[b, i / 2, j / 2, c] + b) / keep      x [B, H, W, C] -> y [B, 2H, 2W, C]
+//   jg_drop_pool2_bwd     g[b, i, j, c] = sum over the 2 x 2 cell of dy * m / keep                     dy [B, 2H, 2W, C] -> g [B, H, W, C]
+// with the counter of jg_gn_apply_drop on the materialised upsample (pixel = i * 2W + j).  A thread owns one 16-byte group of one LOW-resolution
+// pixel: one load, one activation, four masks and four stores forward; four loads, four masks and one store backward.
 #include "gn_map.h"
 #include "philox.h"
 
@@ -200,6 +206,69 @@ __global__ __launch_bounds__(256) void drop_bwd_reduce_kernel(const T* __restric
   for (int i = tid; i < 2 * C; i += 256) atomicAdd(&red[(long)b * 2 * C + i], s_acc[i]);
 }
 
+// pixel (2 h + dy) * 2W + 2 w + dx of the high-resolution map, for dy, dx in {0, 1}: k = 2 dy + dx
+__device__ __forceinline__ long up2_pixel(int h, int w, int W, int k) { return (long)(2 * h + (k >> 1)) * (2 * W) + 2 * w + (k & 1); }
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void drop_apply_up2_kernel(const T* __restrict__ x, long ldx, const float* __restrict__ ab, T* __restrict__ y, long ldy,
+                                                             const float* __restrict__ u, const uint32_t* __restrict__ key, uint32_t stream,
+                                                             uint32_t call, float keep, int B, int H, int W, int C, int G) {
+  const DropSrc d = drop_src(u, key, stream, call, keep);
+  const long HW = (long)H * W, HW4 = 4 * HW;
+  const long total = (long)B * HW * G;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+    const int co = (int)(i % G);
+    const long bp = i / G;
+    const int b = (int)(bp / HW);
+    const int lp = (int)(bp - (long)b * HW);
+    const int h = lp / W, w = lp - h * W;
+    const uint4 v = *reinterpret_cast<const uint4*>(x + bp * ldx + co * 8);
+    float a[8], bb[8], f[8], r[8], m[8];
+    load_ab(ab, b, C, co, a, bb);
+    unpack8<T>(v, f);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) f[q] = act_f<ACT>(a[q] * f[q] + bb[q]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long pix = up2_pixel(h, w, W, k);
+      drop_factors(d, b, pix, co, C, HW4, m);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) r[q] = m[q] != 0.f ? f[q] * m[q] : 0.f;      // a dropped element is exactly 0
+      *reinterpret_cast<uint4*>(y + ((long)b * HW4 + pix) * ldy + co * 8) = pack8<T>(r);
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void drop_pool2_bwd_kernel(const T* __restrict__ dy, long lddy, T* __restrict__ g, long ldg, const float* __restrict__ u,
+                                                             const uint32_t* __restrict__ key, uint32_t stream, uint32_t call, float keep, int B, int H,
+                                                             int W, int C, int G) {
+  const DropSrc d = drop_src(u, key, stream, call, keep);
+  const long HW = (long)H * W, HW4 = 4 * HW;
+  const long total = (long)B * HW * G;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+    const int co = (int)(i % G);
+    const long bp = i / G;
+    const int b = (int)(bp / HW);
+    const int lp = (int)(bp - (long)b * HW);
+    const int h = lp / W, w = lp - h * W;
+    uint4 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const uint4*>(dy + ((long)b * HW4 + up2_pixel(h, w, W, k)) * lddy + co * 8);
+    float acc[8], f[8], m[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      drop_factors(d, b, up2_pixel(h, w, W, k), co, C, HW4, m);
+      unpack8<T>(v[k], f);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc[q] += m[q] != 0.f ? f[q] * m[q] : 0.f;
+    }
+    *reinterpret_cast<uint4*>(g + bp * ldg + co * 8) = pack8<T>(acc);
+  }
+}
+
 inline bool bad_drop(float keep, const float* u, const uint32_t* key, uint32_t stream, int C) {
   return !(keep > 0.f && keep <= 1.f) || (!u && !key) || stream > 0xffffu || C / 4 > 0xffff;
 }
@@ -264,6 +333,31 @@ extern "C" int jg_gn_bwd_apply_drop(int dtype, const void* x, int64_t ldx, const
                                                               (const T*)x, (long)ldx, (const T*)dy, (long)lddy, ab, pqr, (T*)dx, (long)lddx, u, key,
                                                               stream, call, keep, B, HW, C, G);););
   }
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+
+// the low-resolution side is [B, H, W, C], the high-resolution side [B, 2H, 2W, C]: its pixel index 4 H W - 1 has to fit the 32-bit counter word
+inline bool bad_up2(int B, int H, int W, int C) { return H < 1 || W < 1 || (long)H * W > 0x7fffffffL / 4 || bad_shape(B, H * W, C); }
+
+extern "C" int jg_gn_apply_drop_up2(int dtype, const void* x, int64_t ldx, const float* ab, void* y, int64_t ldy, int B, int H, int W, int C, int act,
+                                    float keep, const float* u, const uint32_t* key, uint32_t stream, uint32_t call, jg_stream_t s) {
+  if (bad_up2(B, H, W, C) || bad_ld(x, ldx, C) || bad_ld(y, ldy, C) || bad_tab(ab, nullptr) || bad_drop(keep, u, key, stream, C)) return JG_ERR_BAD_ARG;
+  if (act != JG_ACT_NONE && act != JG_ACT_RELU && act != JG_ACT_LRELU && act != JG_ACT_SILU) return JG_ERR_BAD_ARG;
+  const int G = C / 8;
+  JG_DISPATCH_DTYPE(dtype, JG_DISPATCH_ACT(act, hipLaunchKernelGGL((drop_apply_up2_kernel<T, ACT>), dim3(stream_grid((long)B * H * W * G)), dim3(256), 0,
+                                                            (hipStream_t)s, (const T*)x, (long)ldx, ab, (T*)y, (long)ldy, u, key, stream, call, keep, B,
+                                                            H, W, C, G);););
+  JG_CHECK_LAUNCH();
+  return JG_OK;
+}
+
+extern "C" int jg_drop_pool2_bwd(int dtype, const void* dy, int64_t lddy, void* g, int64_t ldg, int B, int H, int W, int C, float keep, const float* u,
+                                 const uint32_t* key, uint32_t stream, uint32_t call, jg_stream_t s) {
+  if (bad_up2(B, H, W, C) || bad_ld(dy, lddy, C) || bad_ld(g, ldg, C) || bad_drop(keep, u, key, stream, C)) return JG_ERR_BAD_ARG;
+  const int G = C / 8;
+  JG_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((drop_pool2_bwd_kernel<T>), dim3(stream_grid((long)B * H * W * G)), dim3(256), 0, (hipStream_t)s,
+                                              (const T*)dy, (long)lddy, (T*)g, (long)ldg, u, key, stream, call, keep, B, H, W, C, G););
   JG_CHECK_LAUNCH();
   return JG_OK;
 }

@@ -204,6 +204,25 @@ def gn_bwd_apply_drop(x, dy, ab, pqr, act, keep, u, key, stream, call):
     return dx
 
 
+def gn_apply_drop_up2(x, ab, act, keep, u, key, stream, call):
+    """y [B, 2H, 2W, C] = m * act(a up2(x) + b) / keep from x [B, H, W, C] (rows may be a channel slice): the mask of gn_apply_drop on the
+    materialised upsample; u fp32 [B, C, 2H, 2W] or None = drawn"""
+    B, H, W, C = x.shape
+    y = torch.empty((B, 2 * H, 2 * W, C), device=x.device, dtype=x.dtype)
+    check(_lib.lib().jg_gn_apply_drop_up2(_dt(x), x.data_ptr(), x.stride(2), _p(ab), y.data_ptr(), C, B, H, W, C, act, keep, _p(u), _p(key), stream,
+                                          call, _st()), "jg_gn_apply_drop_up2")
+    return y
+
+
+def drop_pool2_bwd(dy, keep, u, key, stream, call):
+    """g [B, H, W, C] = 2 x 2 sums of dy * m / keep from dy [B, 2H, 2W, C]: the adjoint of gn_apply_drop_up2's mask and upsample"""
+    B, H2, W2, C = dy.shape
+    g = torch.empty((B, H2 // 2, W2 // 2, C), device=dy.device, dtype=dy.dtype)
+    check(_lib.lib().jg_drop_pool2_bwd(_dt(dy), dy.data_ptr(), dy.stride(2), g.data_ptr(), C, B, H2 // 2, W2 // 2, C, keep, _p(u), _p(key), stream,
+                                       call, _st()), "jg_drop_pool2_bwd")
+    return g
+
+
 # ---- reflection padding, bilinear resize -----------------------------------------------------------------------------------------------
 def reflect_pad2d(x, pad):
     B, H, W, C = x.shape

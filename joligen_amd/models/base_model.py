@@ -21,7 +21,7 @@ from contextlib import ExitStack
 
 import torch
 
-from .. import parallel
+from .. import ops, parallel
 from ..optim import FusedAdamW
 
 
@@ -222,8 +222,24 @@ class BaseModel:
                 param.requires_grad = requires_grad and not frozen
 
     # ---- step driver (:1302-1377) --------------------------------------------------------------
+    def bind_unet_dropout(self, unet, prefix):
+        """G_dropout of a diffusion UNet: its placeholders get the paths the reference gives the modules below netG_A, and this model draws
+        the Philox key of their masks once per optimize_parameters()"""
+        from ..modules.dropout import bind_dropout
+
+        bind_dropout(unet, unet.dropout_state, prefix)
+        self.unet_dropout_state = unet.dropout_state if unet.dropout else None
+
+    def begin_dropout_step(self):
+        """a new step for the UNet's dropout masks: invocation counters back to 0 and a fresh key (kept when uniforms are injected).  Nothing is
+        drawn for a network without dropout."""
+        st = getattr(self, "unet_dropout_state", None)
+        if st is not None and self.opt.isTrain:
+            st.begin_step(ops.d_aug_key(self.device) if st.rand is None else None)
+
     def optimize_parameters(self):
         self.niter += 1
+        self.begin_dropout_step()
         self._ema_fused_this_iter = set()
         with ExitStack() as stack:
             if len(self.opt.gpu_ids) > 1 and self.niter % self.opt.train_iter_size != 0:

@@ -70,6 +70,7 @@ class CMModel(BaseModel):
         opt.alg_diffusion_cond_embed = opt.alg_diffusion_cond_image_creation
         opt.alg_diffusion_cond_embed_dim = 32 if opt.alg_diffusion_ddpm_cm_ft else 256
         self.netG_A = define_G_cm(opt)
+        self.bind_unet_dropout(self.netG_A.cm_model, "cm_model.")
         if opt.isTrain:
             self.netG_A.current_t = max(self.netG_A.current_t, getattr(opt, "total_iters", 0))   # :200-203
         self.model_names = ["G_A"]

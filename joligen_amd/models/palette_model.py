@@ -84,6 +84,7 @@ class PaletteModel(BaseModel):
             opt.G_nblocks = 2  # palette_model.py:199-203
 
         self.netG_A = define_G(**vars(opt))
+        self.bind_unet_dropout(self.netG_A.denoise_fn.model, "denoise_fn.model.")
         self.model_names = ["G_A"]
         if opt.isTrain:
             self.optimizer_G = self.make_optimizer(self.netG_A, lr=opt.train_G_lr, betas=(opt.train_beta1, opt.train_beta2),

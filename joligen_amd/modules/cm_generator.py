@@ -171,13 +171,20 @@ class CMGenerator(nn.Module):
             if side is None:
                 side = self.__dict__["_fork_stream"] = torch.cuda.Stream(device=dev)
             side.wait_stream(main)
+            # G_dropout: a key that no step driver has given is drawn here, in front of the fork, not on the side stream; the reference invokes the student first; the teacher, issued first here, is invocation 1 of every Dropout, the student 0
+            if self.cm_model.dropout and self.cm_model.training:
+                self.cm_model.dropout_state.ensure_key(dev)
+                side.wait_stream(main)
+            self.cm_model.shift_dropout_calls(1)
             with torch.cuda.stream(side), torch.no_grad():
                 current_noisy_x, xin_cur = ops.cm_noisy(x, noise, current_sigmas, mask, x_cond, self.act_dtype, cpad)
                 F_cur = self._unet(xin_cur, current_sigmas)
+            self.cm_model.shift_dropout_calls(-2)
             for t in (x, noise, current_sigmas, mask, x_cond):
                 if t is not None and t.is_cuda:
                     t.record_stream(side)
             F_next = self._unet(xin_next, next_sigmas)
+            self.cm_model.shift_dropout_calls(1)
             main.wait_stream(side)
             F_cur.record_stream(main)
             current_noisy_x.record_stream(main)

@@ -23,17 +23,31 @@ class DropoutState:
         if key is not None:
             self.key = key
 
-    def next(self, m, x):
-        """the dropout arguments of ops.group_norm / ops.activation_dropout for this invocation of placeholder `m` on x [B, H, W, C]"""
-        call = self.calls.get(m.stream, 0)
+    def ensure_key(self, device):
+        """a state nobody has given a key (no step driver) draws one, on the current stream; injected uniforms need none"""
+        if self.rand is None and self.key is None:
+            from .. import ops
+
+            self.key = ops.d_aug_key(device)
+
+    def next(self, m, x=None, shape=None, device=None, call=None, key=None, keep=None):
+        """the dropout arguments of ops.group_norm / ops.activation_dropout for one invocation of placeholder `m` on x [B, H, W, C] (or a mask
+        of `shape` on `device`).  call / key None: the placeholder's next invocation and this state's key; given (the fused schedule of the
+        diffusion UNet names the call and key of its node): the counter moves past `call`.  keep None: 1 - m.p."""
+        if x is not None:
+            shape, device = x.shape, x.device
+        if call is None:
+            call = self.calls.get(m.stream, 0)
         self.calls[m.stream] = call + 1
         u = None
         if self.rand is not None:
-            B, H, W, C = x.shape
-            u = self.rand(m.path, call, (B, C, H, W), x.device)
-        elif self.key is None:
-            raise RuntimeError(f"dropout {m.path or m.stream}: no Philox key (DropoutState.begin_step(ops.d_aug_key(device))) and no dropout_rand")
-        return dict(keep=1.0 - m.p, u=u, key=self.key, stream=m.stream, call=call)
+            B, H, W, C = shape
+            u = self.rand(m.path, call, (B, C, H, W), device)
+        elif key is None:
+            key = self.key
+            if key is None:
+                raise RuntimeError(f"dropout {m.path or m.stream}: no Philox key (DropoutState.begin_step(ops.d_aug_key(device))) and no dropout_rand")
+        return dict(keep=1.0 - m.p if keep is None else keep, u=u, key=key, stream=m.stream, call=call)
 
 
 class FusedDropout(nn.Dropout):

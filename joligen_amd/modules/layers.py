@@ -99,8 +99,9 @@ class GroupNorm(nn.Module):
         super().__init__()
         self.norm = nn.GroupNorm(group_size, channels)
 
-    def forward(self, x, film=None, act=ops.JG_ACT_NONE):
-        return ops.group_norm(x, self.norm.num_groups, self.norm.weight, self.norm.bias, film, act, self.norm.eps)
+    def forward(self, x, film=None, act=ops.JG_ACT_NONE, **drop):
+        """drop: the dropout arguments of ops.group_norm (keep, u, key, stream, call), none without dropout"""
+        return ops.group_norm(x, self.norm.num_groups, self.norm.weight, self.norm.bias, film, act, self.norm.eps, **drop)
 
 
 def zero_module(module):

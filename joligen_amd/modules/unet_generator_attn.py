@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops import JG_ACT_NONE, JG_ACT_SILU
+from .dropout import DropoutOwner, DropoutState, FusedDropout, bind_dropout
 from .layers import GroupNorm, JGConv1d, JGConv2d, zero_module
 
 
@@ -64,13 +65,29 @@ class ResBlock(EmbedBlock):
         self.in_layers = nn.Sequential(normalization(channels, norm), nn.SiLU(),
                                        JGConv2d(channels, self.out_channel, 3, padding=1))
         self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_channels, 2 * self.out_channel))
-        self.out_layers = nn.Sequential(normalization(self.out_channel, norm), nn.SiLU(), nn.Dropout(p=dropout),
+        self.out_layers = nn.Sequential(normalization(self.out_channel, norm), nn.SiLU(), FusedDropout(p=dropout),
                                         zero_module(JGConv2d(self.out_channel, self.out_channel, 3, padding=1)))
         if self.out_channel == channels:
             self.skip_connection = nn.Identity()
         else:
             self.skip_connection = JGConv2d(channels, self.out_channel, 1)
         self.emb_slice = None  # (offset, n) into the stacked embedding projection, set by UNet
+
+    def drop_live(self):
+        """nn.Dropout(p) of out_layers (unet_generator_attn.py:207-215 of the reference) is on: p > 0 in training"""
+        return bool(self.dropout) and self.training
+
+    def drop_args(self, shape, device, call=None, key=None):
+        """the dropout arguments of this invocation of out_layers[2] for a mask of `shape` [B, H, W, C] (ops.group_norm(keep=...), the executor's
+        jg_gn_apply_drop*): DropoutState.next on the placeholder with the rate `self.dropout` as it stands now (the tests and the legacy hook
+        set it from outside; the placeholder's own p is what the block was built with).  A block outside a UNet gets a state of its own; a
+        state nobody has given a key draws one."""
+        d = self.out_layers[2]
+        if d.state is None:
+            bind_dropout(self, DropoutState())
+        if key is None:
+            d.state.ensure_key(device)
+        return d.state.next(d, shape=shape, device=device, call=call, key=key, keep=1.0 - float(self.dropout))
 
     def forward(self, x, emb):
         """x: [B,H,W,C] 16-bit.  emb: either the raw embedding [B, emb_channels] (fp32) or an
@@ -94,14 +111,16 @@ class ResBlock(EmbedBlock):
                 h = conv1(h)
         else:
             h = conv1(h)
-        h = self.out_layers[0](h, film=emb_out, act=JG_ACT_SILU)  # GN * (1+scale) + shift, SiLU
-        if self.dropout and self.training:
-            # nn.Dropout(p) of out_layers (unet_generator_attn.py:207-215 of the reference): element-wise Bernoulli(1 - p) mask scaled by
-            # 1 / (1 - p), between the activation and the second convolution.  No BASELINE config sets G_dropout / a UNet dropout > 0:
-            # the mask is a torch device op on the module-by-module graph (the fused schedule hands such networks over to it);
-            # `dropout_rand` (callable(shape, device) -> uniforms) injects the draws for parity runs.
-            src = getattr(self, "dropout_rand", None)
-            u = src(h.shape, h.device) if src is not None else torch.rand(h.shape, device=h.device)
+        legacy = getattr(self, "dropout_rand", None) if self.drop_live() else None
+        if self.drop_live() and legacy is None:
+            # the mask rides in the GroupNorm + FiLM + SiLU pass (csrc/dropout.hip) and is regenerated, never stored, by its backward
+            h = self.out_layers[0](h, film=emb_out, act=JG_ACT_SILU, **self.drop_args(h.shape, h.device))
+        else:
+            h = self.out_layers[0](h, film=emb_out, act=JG_ACT_SILU)  # GN * (1+scale) + shift, SiLU
+        if legacy is not None:
+            # parity hook of before the fused mask: `dropout_rand` = callable(shape_NHWC, device) -> uniforms set on the BLOCK, draws taken in
+            # block order.  Such a block keeps the torch mask (and takes its network off the fused schedule): DESIGN.md, UNet dropout
+            u = legacy(h.shape, h.device)
             keep = 1.0 - float(self.dropout)
             h = h * ((u < keep).to(h.dtype) * (1.0 / keep if keep > 0.0 else 0.0))
         skipw = 1.0 / math.sqrt(2) if self.efficient else 1.0
@@ -144,7 +163,7 @@ class _EmbAll:
         self.all = all_
 
 
-class UNet(nn.Module):
+class UNet(nn.Module, DropoutOwner):
     def __init__(self, image_size, in_channel, inner_channel, out_channel, res_blocks, attn_res, tanh,
                  n_timestep_train, n_timestep_test, norm, group_norm_size, cond_embed_dim, dropout=0,
                  channel_mults=(1, 2, 4, 8), conv_resample=True, use_checkpoint=False, use_fp16=False, num_heads=1,
@@ -211,6 +230,21 @@ class UNet(nn.Module):
                 m.emb_slice = (off, 2 * m.out_channel)
                 off += 2 * m.out_channel
         self.emb_total = off
+        # one DropoutState for the out_layers[2] placeholders: a stream each, paths as the reference names the modules (the owner of this
+        # network binds again with its own prefix, e.g. "denoise_fn.model.")
+        self.dropout_state = DropoutState()
+        bind_dropout(self, self.dropout_state)
+        self._res_blocks = [m for m in self.modules() if isinstance(m, ResBlock)]
+
+    def shift_dropout_calls(self, n):
+        """move the invocation counter of every live placeholder by n: a caller that issues two forwards in another order than the reference
+        invokes them (the forked no-grad teacher of the consistency model) numbers them as the reference does"""
+        if self.dropout and self.training:
+            calls = self.dropout_state.calls
+            for rb in self._res_blocks:
+                if rb.dropout:
+                    s = rb.out_layers[2].stream
+                    calls[s] = calls.get(s, 0) + n
 
     # -- forward ---------------------------------------------------------------------------
     def _emb_all(self, emb):
@@ -245,15 +279,19 @@ class UNet(nn.Module):
         With a finalised arena the whole network runs as ONE autograd node on the fused schedule of
         unet_exec.py (same kernels, no concat / statistics / gradient-add passes); `jg_fused = False`
         selects the module-by-module graph below (what the parity tests compare it against)."""
-        drop = bool(self.dropout) and self.training        # dropout > 0 in training: the module-by-module graph (ResBlock.forward) has the mask
-        if getattr(self, "jg_fused", True) and getattr(self, "_jg_arena_ref", None) is not None and input.is_cuda and not drop \
+        drop = bool(self.dropout) and self.training and any(rb.dropout for rb in self._res_blocks)
+        # a block with the legacy `dropout_rand` hook keeps its torch mask: the module-by-module graph (ResBlock.forward)
+        legacy = drop and any(getattr(rb, "dropout_rand", None) is not None for rb in self._res_blocks)
+        if drop:
+            self.dropout_state.ensure_key(input.device)       # (no step driver: drawn here, once, for either graph)
+        if getattr(self, "jg_fused", True) and getattr(self, "_jg_arena_ref", None) is not None and input.is_cuda and not legacy \
                 and not ops.TORCH_OPS_BOUNDARY:
             from .unet_exec import fused_unet
 
             if embed_gammas is None:
                 embed_gammas = torch.ones((input.shape[0], self.cond_embed_dim), device=input.device)
             emb = self._emb_all(embed_gammas.float().contiguous())
-            return fused_unet(self, input, emb.all)
+            return fused_unet(self, input, emb.all, drop=drop)
         h, hs, emb = self.compute_feats(input, embed_gammas)
         for module in self.output_blocks:
             h = ops.cat_channels(h, hs.pop())

@@ -689,13 +689,13 @@ def zeros_f32(n, device):
     return out
 
 
-def _drop_args(x, keep, u, key, stream, call):
+def _drop_args(x, keep, u, key, stream, call, shape=None):
     """the checked dropout arguments (keep, u, key, stream, call) of the fused passes of csrc/dropout.hip: u fp32 [B, C, H, W] injected uniforms
-    or None = drawn in the kernel from the two-word device tensor `key` (d_aug_key)"""
+    or None = drawn in the kernel from the two-word device tensor `key` (d_aug_key); shape: that of the mask [B, H, W, C] where it is not x's"""
     keep, stream, call = float(keep), int(stream), int(call)
     if x.dim() != 4 or not 0.0 < keep <= 1.0 or not 0 <= stream < 65536 or not 0 <= call < 2 ** 32:
         raise ValueError(f"dropout: x [B, H, W, C], keep in (0, 1], stream < 65536 (got {tuple(x.shape)}, keep={keep}, stream={stream}, call={call})")
-    B, H, W, C = x.shape
+    B, H, W, C = x.shape if shape is None else shape
     if u is not None:
         if u.dtype != torch.float32 or tuple(u.shape) != (B, C, H, W):
             raise ValueError(f"dropout: u must be fp32 [B, C, H, W] = {(B, C, H, W)}, got {u.dtype} {tuple(u.shape)}")
@@ -2465,6 +2465,44 @@ def _ad_backward(ctx, dy):
 
 
 _op_act_drop.register_autograd(_ad_backward, setup_context=_ad_setup)
+
+
+# the two passes of a dropout behind a low-resolution GroupNorm + nearest 2x upsample (the up-blocks of the efficient diffusion UNet on the fused
+# schedule, modules/unet_exec.py): plain functional kernels, the schedule's hand-written backward chains them
+@torch.library.custom_op("jg355::gn_apply_drop_up2", mutates_args=())
+def _op_gn_apply_drop_up2(x: torch.Tensor, ab: Optional[torch.Tensor], act: int, keep: float, u: Optional[torch.Tensor], key: Optional[torch.Tensor],
+                          stream: int, call: int) -> torch.Tensor:
+    """y [B, 2H, 2W, C] = m * act(a up2(x) + b) / keep from x [B, H, W, C]; ab fp32 [B, C, 2] (None: a = 1, b = 0); u fp32 [B, C, 2H, 2W] or None
+    = drawn from `key` on the counter of the high-resolution map"""
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    if ab is not None:
+        if ab.dtype != torch.float32 or tuple(ab.shape) != (B, C, 2):
+            raise ValueError(f"gn_apply_drop_up2: ab must be fp32 [B, C, 2] = {(B, C, 2)}, got {ab.dtype} {tuple(ab.shape)}")
+        ab = ab.contiguous()
+        _require_cuda(ab)
+    return launch.gn_apply_drop_up2(x, ab, act, *_drop_args(x, keep, u, key, stream, call, shape=(B, 2 * H, 2 * W, C)))
+
+
+@_op_gn_apply_drop_up2.register_fake
+def _(x, ab, act, keep, u, key, stream, call):
+    B, H, W, C = x.shape
+    return x.new_empty((B, 2 * H, 2 * W, C))
+
+
+@torch.library.custom_op("jg355::drop_pool2_bwd", mutates_args=())
+def _op_drop_pool2_bwd(dy: torch.Tensor, keep: float, u: Optional[torch.Tensor], key: Optional[torch.Tensor], stream: int, call: int) -> torch.Tensor:
+    """g [B, H, W, C] = 2 x 2 sums of dy * m / keep from dy [B, 2H, 2W, C], the mask of gn_apply_drop_up2 regenerated"""
+    dy = dy.contiguous()
+    if dy.dim() != 4 or dy.shape[1] % 2 or dy.shape[2] % 2:
+        raise ValueError(f"drop_pool2_bwd: dy [B, 2H, 2W, C], got {tuple(dy.shape)}")
+    return launch.drop_pool2_bwd(dy, *_drop_args(dy, keep, u, key, stream, call))
+
+
+@_op_drop_pool2_bwd.register_fake
+def _(dy, keep, u, key, stream, call):
+    B, H2, W2, C = dy.shape
+    return dy.new_empty((B, H2 // 2, W2 // 2, C))
 
 
 @torch.library.custom_op("jg355::attention_core", mutates_args=())
