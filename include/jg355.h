@@ -678,6 +678,25 @@ int jg_d_aug(int dtype, const void* src, int nd, const void* const* alt, const f
              uint32_t call, int B, int H, int W, int C, int Cpad, jg_stream_t s);
 int jg_apa_update(int dtype, const void* pred, int64_t n, int64_t stride, float* p, float* adjust, float* s_out, float target, float num,
                   float den, jg_stream_t s);
+/* data_online_context_pixels (models/base_model.py:389-431 set_input, :609-636 compute_fake_with_context; models/base_gan_model.py:186-215
+ * mask_context): the generator works on the centre crop, the discriminators judge it inside its surroundings.  H, W are the FRAMED sizes
+ * (crop + 2 c); the window is rows [c, H - c) x columns [c, W - c).  16-bit NHWC tensors, Cpad % 8 == 0, C valid channels, the padding
+ * channels of every output are +0 (csrc/context.hip).
+ *   jg_context_split : x fp32 NCHW [B, C, H, W], read once -> ctx [B, H, W, Cpad] (what jg_nchw_f32_to_nhwc writes, bit for bit) and
+ *                      crop [B, H - 2c, W - 2c, Cpad] = ctx[:, c:-c, c:-c].
+ *   jg_context_frame : out [B, H, W, Cpad] = inner [B, H - 2c, W - 2c, Cpad] inside the window, ctx [B, H, W, Cpad] on the frame: the
+ *                      reference's pad(inner, c) + mask * ctx written as a select (equal to it for finite inputs; a NaN or Inf of the hidden
+ *                      part of ctx does not leak through 0 * x).  out_noisy (or NULL) = out + sigma * z over the whole framed image, the sum
+ *                      in fp32 and rounded once; z: fp32 [B, C, H, W] or NULL: drawn in the kernel exactly as jg_d_aug draws it -- counter
+ *                      (pixel h * W + w of the framed grid, sample, noise_stream | channel group << 16, call), key = two words in DEVICE
+ *                      memory -- so that out_noisy is bit-identical to jg_d_aug(src = out) with the same sigma / key / noise_stream / call.
+ *                      The adjoint with respect to inner is the window of the incoming gradient: jg_crop2d.
+ *   JG_ERR_UNSUPPORTED: a dtype other than JG_F16 / JG_BF16.  JG_ERR_BAD_ARG: c < 1, a window that is empty (H - 2c < 1 or W - 2c < 1),
+ *   C outside 1..Cpad, Cpad not a multiple of 8, a NULL or misaligned (16 bytes) tensor, outputs aliasing inputs or each other, sigma != 0
+ *   without out_noisy or with neither z nor key, sigma NaN, noise_stream above 65535. */
+int jg_context_split(int dtype, const float* x, void* ctx, void* crop, int B, int C, int H, int W, int c, int Cpad, jg_stream_t s);
+int jg_context_frame(int dtype, const void* inner, const void* ctx, void* out, void* out_noisy, float sigma, const float* z, const uint32_t* key,
+                     uint32_t noise_stream, uint32_t call, int B, int H, int W, int c, int C, int Cpad, jg_stream_t s);
 /* nn.Dropout behind a normalise + activate pass (G_dropout of the ResNet generator: resnet_generator.py:62-88; D_dropout of the PatchGAN:
  * discriminators.py:51-108), computed inside that pass and its two backward passes on 16-bit NHWC [B, H*W, C] tensors with pixel strides
  * (C % 8 == 0, strides multiples of 8, pointers 16-byte aligned).  ab: the [B][C][2] table of jg_gn_coef, or NULL = no normalisation

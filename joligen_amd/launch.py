@@ -254,6 +254,29 @@ def bilinear2_bwd(dy, H, W, align_corners):
     return dx
 
 
+# ---- data_online_context_pixels: the crop and its framed image (csrc/context.hip) ------------------------------------------------------------
+def context_split(x, c, act_dtype, cpad=None):
+    """x fp32 NCHW [B, C, H, W] (contiguous), read once -> (ctx [B, H, W, cpad], crop [B, H - 2c, W - 2c, cpad] = ctx[:, c:-c, c:-c]), 16-bit NHWC"""
+    B, C, H, W = x.shape
+    cpad = cpad or (C + 7) // 8 * 8
+    ctx = torch.empty((B, H, W, cpad), device=x.device, dtype=act_dtype)
+    crop = torch.empty((B, max(H - 2 * c, 0), max(W - 2 * c, 0), cpad), device=x.device, dtype=act_dtype)
+    check(_lib.lib().jg_context_split(_DT[act_dtype], x.data_ptr(), ctx.data_ptr(), crop.data_ptr(), B, C, H, W, c, cpad, _st()), "jg_context_split")
+    return ctx, crop
+
+
+def context_frame(inner, ctx, c, C, sigma, z, key, noise_stream, call, out=None, out_noisy=None, want_noisy=False):
+    """out = inner inside the window of ctx, ctx on the frame; out_noisy = out + sigma z (written when `out_noisy` is given or `want_noisy`); z fp32
+    [B, C, H, W] of the framed size or None: drawn in the kernel from the two words of `key` -> (out, out_noisy or None)"""
+    B, H, W, cpad = ctx.shape
+    out = torch.empty_like(ctx) if out is None else out
+    if out_noisy is None and want_noisy:
+        out_noisy = torch.empty_like(ctx)
+    check(_lib.lib().jg_context_frame(_dt(ctx), inner.data_ptr(), ctx.data_ptr(), out.data_ptr(), _p(out_noisy), sigma, _p(z), _p(key), noise_stream,
+                                      call, B, H, W, c, C, cpad, _st()), "jg_context_frame")
+    return out, out_noisy
+
+
 # ---- fp32 linear -----------------------------------------------------------------------------------------------------------------------
 def linear_fwd(x, W, b, act):
     """y = act(x) @ W.T + b, fp32"""

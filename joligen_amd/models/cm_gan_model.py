@@ -41,6 +41,8 @@ def check_cm_gan_options(opt):
             raise NotImplementedError(f"{flag} is outside the SURVEY.md 8 hot path")
     if opt.dataaug_D_noise > 0:
         raise NotImplementedError("dataaug_D_noise: noisy-D terms are outside the built path")
+    if int(getattr(opt, "data_online_context_pixels", 0) or 0) > 0:      # the fused head (ops.cm_gan_head) hands the discriminators the crop: no frame
+        raise NotImplementedError("data_online_context_pixels > 0 with model_type='cm_gan': the seam kernel has no context frame (cut_model has)")
     for name, built in (("D_dropout", False), ("D_spectral", False), ("D_norm", "instance")):
         if getattr(opt, name, built) != built:
             raise NotImplementedError(f"{name}={getattr(opt, name)!r}: only {built!r} is built for the PatchGAN")

@@ -3,8 +3,9 @@
 `calculate_feats` :848-887, `calculate_NCE_loss` :889-909) and models/base_gan_model.py (`compute_D_loss(_generic)`
 :341-419, `compute_G_loss_GAN(_generic)` :421-503) for the default configuration: G_netG='resnet', D_netDs=['basic'],
 alg_cut_netF='mlp_sample', alg_cut_nce_loss in {'monce', 'patchnce', 'SRC_hDCE'}, nce_idt, lsgan, optionally the paired pixel loss
-(alg_cut_supervised_loss 'L1' / 'MSE') and the identity pixel loss (alg_cut_MSE_idt), no semantic / multimodal / context / temporal /
-augmentation branches; the semantic-consistency class branch train_semantic_cls (a classifier as third network group, ops.cls_loss); the discriminator regularisers dataaug_D_noise (Gaussian noise on both discriminator inputs) and dataaug_APA
+(alg_cut_supervised_loss 'L1' / 'MSE') and the identity pixel loss (alg_cut_MSE_idt), no semantic-mask / multimodal / temporal /
+augmentation branches; data_online_context_pixels (the discriminators judge the translated crop inside its real surroundings: ops.context_split /
+ops.context_frame); the semantic-consistency class branch train_semantic_cls (a classifier as third network group, ops.cls_loss); the discriminator regularisers dataaug_D_noise (Gaussian noise on both discriminator inputs) and dataaug_APA
 (adaptive pseudo augmentation) run through ops.d_aug / ops.apa_update, dataaug_D_diffusion (Diffusion-GAN noise on the projected
 discriminator's backbone features) inside that discriminator through ops.d_diffusion / ops.d_diffusion_update.
 
@@ -98,6 +99,37 @@ def check_d_aug_options(opt):
         if len(opt.D_netDs) > ops.D_AUG_MAX:
             raise NotImplementedError(f"dataaug_APA with more than {ops.D_AUG_MAX} discriminators")
     return sigma, apa
+
+
+CONTEXT_VISUAL_NAMES = ["real_A_with_context_vis", "real_B_with_context_vis", "fake_B_with_context_vis", "mask_context_vis"]      # cut_model.py:485-490
+
+
+def check_context_options(opt):
+    """data_online_context_pixels (base_model.py:134 `margin`, :389-431 set_input, :609-636 compute_fake_with_context; base_gan_model.py:186-215
+    mask_context) as this build accepts it; returns c, the width of the frame the discriminators see around the crop (0: off).  The reference
+    multiplies a mask of model_input_nc channels into an image of model_output_nc channels: the two must agree.  Host-only (no device)."""
+    import numbers
+
+    if not hasattr(opt, "data_online_context_pixels"):
+        opt.data_online_context_pixels = 0
+    c = opt.data_online_context_pixels
+    if isinstance(c, bool) or not isinstance(c, numbers.Integral) or c < 0:
+        raise ValueError(f"data_online_context_pixels={c!r}: an integer >= 0 is required")
+    c = int(c)
+    if c > 0 and getattr(opt, "model_input_nc", 3) != getattr(opt, "model_output_nc", 3):
+        raise ValueError(f"data_online_context_pixels={c}: the frame of real_A surrounds fake_B: model_input_nc={opt.model_input_nc!r} must equal "
+                         f"model_output_nc={opt.model_output_nc!r}")
+    return c
+
+
+def check_context_discriminators(opt, c):
+    """the discriminators run on (data_crop_size + 2 c)^2 images (gan_networks.py:349-415).  The PatchGAN takes any size; the projected
+    discriminators resize to D_proj_interp first, and without it their feature network is built for the framed size, which its four strides
+    must divide.  Host-only (no device)."""
+    size = int(opt.data_crop_size) + 2 * c
+    if c > 0 and "projected_d" in opt.D_netDs and int(getattr(opt, "D_proj_interp", -1)) <= 0 and size % 32:
+        raise NotImplementedError(f"data_online_context_pixels={c} with projected_d and no D_proj_interp: the framed size {size} is not a multiple "
+                                  "of 32 (the feature network's deepest stride); set D_proj_interp or choose c so that it is")
 
 
 DROPOUT_GENERATORS = ("resnet", "resnet_9blocks", "resnet_6blocks")      # gan_networks.py:112-122: the only G_netG that receive G_dropout
@@ -207,6 +239,8 @@ class CUTModel(BaseModel):
             if getattr(opt, flag, False):
                 raise NotImplementedError(f"{flag} is outside the SURVEY.md 8 hot path")
         check_d_aug_options(opt)
+        self.context = check_context_options(opt)      # c of data_online_context_pixels: 0 = off
+        check_context_discriminators(opt, self.context)
         self.sem_cls = check_sem_cls_options(opt)      # "off" | "CE" | "MSE" | "L1"
         # dataaug_D_diffusion: the projected discriminator noises its own backbone features (modules/projected_d.Diffusion) and its loss
         # calculator moves the strength; nothing of it lives in this model
@@ -282,6 +316,13 @@ class CUTModel(BaseModel):
         self.d_noise, self.d_apa = check_d_aug_options(opt)
         if self.d_apa and opt.isTrain:
             self.visual_names.append(["APA_img"])
+        if self.context:
+            # cut_model.py:483-492: the framed images resized to the crop; made on demand (compute_visuals), not per step
+            self.context_visual_names = list(CONTEXT_VISUAL_NAMES)
+            self.visual_names.append(self.context_visual_names)
+            # the Philox key of the step's dataaug_D_noise: the frame launch of the forward draws the fake batch's noise with it (inside the
+            # captured generator graph), the discriminator half the real batch's -- one buffer, refilled in place, as the dropout key is
+            self._ctx_key = torch.zeros(2, device=self.device, dtype=torch.int32) if self.d_noise > 0.0 and opt.isTrain else None
         self._bind_dropout()
 
     # ---- G_dropout / D_dropout ------------------------------------------------------------------------------------------------------------
@@ -394,10 +435,27 @@ class CUTModel(BaseModel):
 
     # ---- inputs ---------------------------------------------------------------------------------------------------
     def set_input(self, data):
-        self.real_A_nchw = data["A"].to(self.device, non_blocking=True)
-        self.real_B_nchw = data["B"].to(self.device, non_blocking=True)
-        self.real_A = ops.to_nhwc(self.real_A_nchw, self.act_dtype)
-        self.real_B = ops.to_nhwc(self.real_B_nchw, self.act_dtype)
+        c = self.context
+        if c > 0:
+            # base_model.py:389-431: the loader hands over images 2 c larger than the crop; the generator group reads the centre crops
+            # (real_A / real_B), the discriminators the whole images (real_*_with_context).  One launch per domain writes both.
+            S = int(self.opt.data_crop_size)
+            for dom in ("A", "B"):
+                shape = tuple(data[dom].shape)
+                if len(shape) != 4 or shape[2:] != (S + 2 * c, S + 2 * c):
+                    raise ValueError(f"data_online_context_pixels={c}: data[{dom!r}] must be [B, C, {S + 2 * c}, {S + 2 * c}] (data_crop_size {S} "
+                                     f"+ 2 x {c} context pixels), got {shape}")
+                full = data[dom].to(self.device, non_blocking=True).float()
+                framed, crop = ops.context_split(full, c, self.act_dtype)
+                setattr(self, f"real_{dom}_with_context_nchw", full)
+                setattr(self, f"real_{dom}_nchw", full[:, :, c:-c, c:-c])      # the fp32 centre view
+                setattr(self, f"real_{dom}_with_context", framed)
+                setattr(self, f"real_{dom}", crop)
+        else:
+            self.real_A_nchw = data["A"].to(self.device, non_blocking=True)
+            self.real_B_nchw = data["B"].to(self.device, non_blocking=True)
+            self.real_A = ops.to_nhwc(self.real_A_nchw, self.act_dtype)
+            self.real_B = ops.to_nhwc(self.real_B_nchw, self.act_dtype)
         self.batch_size = self.real_A.shape[0]
         if self.sem_cls != "off" and self.opt.isTrain:
             self._set_input_semantic_cls(data)
@@ -457,9 +515,76 @@ class CUTModel(BaseModel):
         else:
             self.fake = self._net("G_A")(self.real)
         self.fake_B = self.fake[:B]
+        if self.context:
+            self._frame_fake()
         if self.opt.alg_cut_nce_idt:
             self.idt_B = self.fake[B:]
         self._feat_calls = 0
+
+    # ---- data_online_context_pixels ---------------------------------------------------------------------------------------------------------
+    @property
+    def real_B_D(self):
+        """the real image as the discriminators see it"""
+        return self.real_B_with_context if self.context else self.real_B
+
+    @property
+    def fake_B_D(self):
+        """the translated image as the discriminators see it (with the generator's autograd history)"""
+        return self.fake_B_with_context if self.context else self.fake_B
+
+    def _frame_fake(self):
+        """compute_fake_with_context (base_model.py:609-636) and, with dataaug_D_noise, the noisy copy of the framed fake (cut_model.py:668-682)
+        from ONE launch: fake_B_with_context carries the generator's gradient into the GAN terms, fake_B_with_context_noisy (detached) goes to
+        the history pool.  The fake batch is drawn first (call index 0), the real batch later by real_D_operands (call index 1) on the same
+        key: the reference's draw order.  The key is drawn here, on the device, into the model's own buffer -- inside graph F when the step
+        is captured."""
+        sigma = self.d_noise if self.opt.isTrain else 0.0
+        z = key = None
+        if sigma > 0.0:
+            z = self.frame_noise_injection(refresh=not torch.cuda.is_current_stream_capturing())
+            if z is None:
+                self._ctx_key.copy_(ops.d_aug_key(self.device))
+                key = self._ctx_key
+            self._d_key = key
+        self.fake_B_with_context, noisy = ops.context_frame(self.fake_B, self.real_A_with_context, self.context, self.opt.model_output_nc, sigma,
+                                                            z=z, key=key, call=0)
+        if sigma > 0.0:
+            self.fake_B_with_context_noisy = noisy
+
+    def frame_noise_injection(self, refresh=True):
+        """parity runs: the injected z of the framed fake batch (`d_aug_injection("z_fake")`) in a buffer of the model's own, one per shape,
+        so that a captured graph F reads the same address at every replay; `refresh` copies this step's draw into it (the step driver does
+        that ahead of a replay, the eager forward here).  None without an injection: the kernel draws."""
+        if not (self.context and self.d_noise > 0.0 and self.opt.isTrain) or self.d_aug_injection is None:
+            return None
+        if not refresh:
+            return self._ctx_z[self._ctx_z_shape]
+        z = self._d_aug_draw("z_fake")
+        if not hasattr(self, "_ctx_z"):
+            self._ctx_z = {}
+        self._ctx_z_shape = tuple(z.shape)
+        buf = self._ctx_z.get(self._ctx_z_shape)
+        if buf is None:
+            buf = self._ctx_z[self._ctx_z_shape] = torch.empty(self._ctx_z_shape, device=self.device, dtype=torch.float32)
+        buf.copy_(z)
+        return buf
+
+    def compute_visuals(self, nb_imgs):
+        """the context visuals of the reference (cut_model.py:483-492), made when the display asks for them: the framed images and the mask
+        resized to the crop by nearest F.interpolate, fp32 NCHW as the reference's are"""
+        super().compute_visuals(nb_imgs)
+        if not self.context or not hasattr(self, "real_A_with_context_nchw"):
+            return
+        import torch.nn.functional as F
+
+        c, size = self.context, tuple(self.real_A_nchw.shape[2:])
+        self.real_A_with_context_vis = F.interpolate(self.real_A_with_context_nchw, size=size)
+        self.real_B_with_context_vis = F.interpolate(self.real_B_with_context_nchw, size=size)
+        if hasattr(self, "fake_B_with_context"):
+            self.fake_B_with_context_vis = F.interpolate(ops.to_nchw_f32(self.fake_B_with_context.detach(), self.opt.model_output_nc), size=size)
+        mask = torch.ones_like(self.real_A_with_context_nchw)      # base_gan_model.py:186-215
+        mask[:, :, c:-c, c:-c] = 0.0
+        self.mask_context_vis = F.interpolate(mask, size=size)[:, 0]
 
     # ---- generator losses ---------------------------------------------------------------------------------------------
     def _fork_gan(self):
@@ -477,7 +602,7 @@ class CUTModel(BaseModel):
             main = torch.cuda.current_stream(self.device)
             side = self.driver.stream("gan_stream")
             side.wait_stream(main)
-            for t in (self.fake_B, self.real_B):
+            for t in (self.fake_B_D, self.real_B_D):
                 t.record_stream(side)
             with torch.cuda.stream(side):
                 self.compute_G_loss_GAN()
@@ -500,7 +625,7 @@ class CUTModel(BaseModel):
         self._dropout_seek(self.discriminators_names, 0)
         for dn in self.discriminators_names:
             lossf = getattr(self, dn + "_loss_calculator")
-            val = self.opt.alg_gan_lambda * lossf.compute_loss_G(self._net(dn), self.real_B, self.fake_B)
+            val = self.opt.alg_gan_lambda * lossf.compute_loss_G(self._net(dn), self.real_B_D, self.fake_B_D)
             setattr(self, "loss_G_GAN_" + dn, val)
             self.loss_G_tot = self.loss_G_tot + val
 
@@ -667,9 +792,11 @@ class CUTModel(BaseModel):
         dataaug_APA `get_random` for the batch the flagged real samples come from.  Returns (fakes, alts or None), one entry per
         discriminator.  With both options off: the pool queries and nothing else."""
         src = self.fake_B
-        if self.d_noise > 0.0 or self.d_apa:
+        if (self.d_noise > 0.0 or self.d_apa) and not (self.context and self.d_noise > 0.0):      # (framed + noisy: the forward drew the step's key)
             self._d_key = ops.d_aug_key(self.device) if self.d_aug_injection is None else None      # one Philox key per step
-        if self.d_noise > 0.0:          # call index 0: the fake batch is drawn first, as in the reference
+        if self.context:                # the forward's frame launch made the framed fake and its noisy copy: the pool stores framed images
+            src = self.fake_B_with_context_noisy if self.d_noise > 0.0 else self.fake_B_with_context
+        elif self.d_noise > 0.0:        # call index 0: the fake batch is drawn first, as in the reference
             (self.fake_B_noisy,), _ = ops.d_aug(self.fake_B, self.opt.model_output_nc, self.d_noise, z=self._d_aug_draw("z_fake"), key=self._d_key, call=0)
             src = self.fake_B_noisy
         fakes, alts = [], [] if self.d_apa else None
@@ -686,15 +813,17 @@ class CUTModel(BaseModel):
         static operands of a captured graph, written in place.  Without APA all discriminators share one operand (`real_B_noisy`); with both
         options off this is real_B itself and nothing is launched."""
         n = len(self.discriminators_names)
+        real = self.real_B_D            # with data_online_context_pixels: real_B_with_context, and every operand below has the framed shape
         if not (self.d_noise > 0.0 or self.d_apa):
-            return [self.real_B] * n
+            return [real] * n
         z = self._d_aug_draw("z_real") if self.d_noise > 0.0 else None
         if not self.d_apa:
-            (self.real_B_noisy,), _ = ops.d_aug(self.real_B, self.opt.model_output_nc, self.d_noise, z=z, key=self._d_key, call=1, outs=outs)
-            return [self.real_B_noisy] * n
+            (noisy,), _ = ops.d_aug(real, self.opt.model_output_nc, self.d_noise, z=z, key=self._d_key, call=1, outs=outs)
+            setattr(self, "real_B_with_context_noisy" if self.context else "real_B_noisy", noisy)
+            return [noisy] * n
         calcs = [getattr(self, dn + "_loss_calculator") for dn in self.discriminators_names]
         us = [self._d_aug_draw("u", d) for d in range(n)]
-        reals, flags = ops.d_aug(self.real_B, self.opt.model_output_nc, self.d_noise, z=z, key=self._d_key, call=1, alts=alts,
+        reals, flags = ops.d_aug(real, self.opt.model_output_nc, self.d_noise, z=z, key=self._d_key, call=1, alts=alts,
                                  ps=[c.apa_state[0:1] for c in calcs], us=None if us[0] is None else us, streams=[c.apa_stream for c in calcs], outs=outs)
         for d, c in enumerate(calcs):
             c.apa_flags = flags[d]

@@ -84,6 +84,8 @@ class GenGraphs:
     fwd: object = None
     bwd: object = None
     outs: dict = None
+    ctx_A: torch.Tensor = None      # data_online_context_pixels: static copies of real_A_with_context / real_B_with_context
+    ctx_B: torch.Tensor = None
 
 
 @dataclass
@@ -105,15 +107,25 @@ class DiscGraph:
 class CUTStepDriver:
     def __init__(self, model):
         self.model, self.drawn_fakes = model, None                   # drawn_fakes: the pool draws of the running step, for compute_D_loss
-        self.d_stream = self.gan_stream = self.wg_stream = None      # created on first use (`stream`)
+        self.d_stream = self.gan_stream = self.wg_stream = self.cap_stream = None      # created on first use (`stream`)
         self.g_half = CapturedHalf(model, "jg_graph_G", "JG_GRAPH_G", "generator", "generator graph dropped", "G")
         self.d_half = CapturedHalf(model, "jg_graph_D", "JG_GRAPH_D", "discriminator", "graph dropped", "1",
                                    "HIP_GRAPHS_SAFE is False (HIP initialised before DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 could be set)")
 
     def stream(self, name):
-        """`d_stream` (discriminator half), `gan_stream` (forked GAN branch of compute_G_loss) or `wg_stream`, created on first use"""
+        """`d_stream` (discriminator half), `gan_stream` (forked GAN branch of compute_G_loss), `wg_stream` or `cap_stream` (the stream the
+        generator graphs are captured on), created on first use.  No two of them are the same HIP stream: torch hands its 32 pool streams out
+        round-robin to every `torch.cuda.Stream()` of the process, and the per-stream scratch of the launch layer (split-K workspace, zeroed
+        rows) is keyed by the raw stream of the launch or of the capture.  The discriminator half and graph B run side by side; when `d_stream`
+        happened to be the pool stream graph B was captured on (torch's process-wide default capture stream, before `cap_stream`), the two
+        shared one split-K workspace and the generator's gradients came out wrong by orders of magnitude -- one process in 32, by the number
+        of streams created before."""
         if getattr(self, name) is None:
-            setattr(self, name, torch.cuda.Stream(device=self.model.device))
+            taken = {getattr(self, n).cuda_stream for n in ("d_stream", "gan_stream", "wg_stream", "cap_stream") if getattr(self, n) is not None}
+            s = torch.cuda.Stream(device=self.model.device)
+            while s.cuda_stream in taken:
+                s = torch.cuda.Stream(device=self.model.device)
+            setattr(self, name, s)
         return getattr(self, name)
 
     # ---- the discriminator half under the generator's backward ------------------------------------------------------------
@@ -149,7 +161,8 @@ class CUTStepDriver:
         if POOL_ON_SIDE:
             # round 6: the draws themselves on the discriminator stream (~40 copy launches per step that graph B no longer queues behind):
             # the pool marks every stored image it reads there (`reader_stream`), the fresh batch is marked here
-            m.fake_B.record_stream(side)
+            for t in self._pool_sources():
+                t.record_stream(side)
             side.wait_stream(torch.cuda.current_stream(m.device))
             with torch.cuda.stream(side):
                 return m.draw_D_fakes(reader_stream=side)
@@ -157,6 +170,14 @@ class CUTStepDriver:
         for f in fakes + (alts or []):
             f.record_stream(side)
         return fakes, alts
+
+    def _pool_sources(self):
+        """what `draw_D_fakes` reads of the generator half's outputs: fake_B, or with data_online_context_pixels the framed fake (and its
+        noisy copy with dataaug_D_noise)"""
+        m = self.model
+        if not m.context:
+            return [m.fake_B]
+        return [m.fake_B_with_context] + ([m.fake_B_with_context_noisy] if m.d_noise > 0.0 else [])
 
     def optimize_parameters(self):
         """the early-D step; `model.step_driver` says which form of each half ran"""
@@ -172,7 +193,7 @@ class CUTStepDriver:
                 getattr(m, fn)()
         self.drawn_fakes = self.draw_pool_fakes(side)
         try:                               # whatever happens below, a later compute_D_loss must query the pool again, not reuse these
-            m.real_B.record_stream(side)
+            m.real_B_D.record_stream(side)
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 m._group_flags(gD)
@@ -225,6 +246,8 @@ class CUTStepDriver:
             return None
         nets = [m._net(n) for n in m.model_names]
         key = (tuple(m.real_A.shape), tuple(m.real_B.shape), m.real_A.dtype, its, float(m.loss_scale))
+        if m.context:                   # the framed shapes: graph F holds static copies of the two with-context images and the frame launch
+            key += (tuple(m.real_A_with_context.shape), tuple(m.real_B_with_context.shape), m.d_aug_injection is not None)
         st = self.g_half.get(key, nets, lambda restore: self._g_capture(its, nets, restore))
         if st is None:
             return None
@@ -234,32 +257,49 @@ class CUTStepDriver:
         st.real_A.copy_(m.real_A)
         st.real_B.copy_(m.real_B)
         m.real_A, m.real_B = st.real_A, st.real_B
+        if m.context:
+            st.ctx_A.copy_(m.real_A_with_context)
+            st.ctx_B.copy_(m.real_B_with_context)
+            m.real_A_with_context, m.real_B_with_context = st.ctx_A, st.ctx_B
+            m.frame_noise_injection()          # parity runs: this step's z of the framed fake into the buffer graph F reads
         st.fwd.replay()
         for n in nets:                     # graph F has just refreshed every trained working copy on the device: the host-side flag follows,
             n.arena._dirty = False         # or the discriminator half would refresh D's copies again on the side stream while graph B reads them
         for k, v in st.outs.items():
             setattr(m, k, v)
         if m.fake_B_pool.pool_size > 0:        # the pool keeps views of what it is handed: not of a buffer the next replay overwrites
-            m.fake_B = m.fake_B.clone()
+            if m.context:                      # (the framed fake, noisy with dataaug_D_noise: CUTModel.draw_D_fakes)
+                name = "fake_B_with_context_noisy" if m.d_noise > 0.0 else "fake_B_with_context"
+                setattr(m, name, getattr(m, name).clone())
+            else:
+                m.fake_B = m.fake_B.clone()
         return st
 
     def _g_capture(self, its, nets, restore):
         m = self.model
         st = GenGraphs(m.real_A.clone(), m.real_B.clone(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
         keep_inputs, rng = (m.real_A, m.real_B), torch.cuda.get_rng_state(m.device)
+        if m.context:
+            st.ctx_A, st.ctx_B = m.real_A_with_context.clone(), m.real_B_with_context.clone()
+            keep_ctx = (m.real_A_with_context, m.real_B_with_context)
+            m.frame_noise_injection()          # (allocated and filled outside the capture)
         try:
             for n in nets:
                 n.arena.ensure_fresh()             # (never-trained working copies: derived now, outside the graph)
                 n.arena._dirty = True              # the refresh of every TRAINED working copy belongs to graph F
             m.real_A, m.real_B = st.real_A, st.real_B
-            with torch.cuda.graph(st.fwd, capture_error_mode="thread_local"):
+            if m.context:
+                m.real_A_with_context, m.real_B_with_context = st.ctx_A, st.ctx_B
+            with torch.cuda.graph(st.fwd, stream=self.stream("cap_stream"), capture_error_mode="thread_local"):
                 ops.zero_pool_reset(m.device, True)          # the zeroed reduction rows of this graph come out of a chunk it clears itself
                 m._forward_core()
                 m.compute_G_loss()
             names = ["fake", "fake_B", "loss_G_tot", "loss_G_NCE"] + ["loss_G_GAN_" + dn for dn in m.discriminators_names]
             names += [k for k in ("loss_G_supervised", "loss_G_MSE_idt") if k[len("loss_"):] in m.loss_names_G]      # the pixel terms that exist
+            if m.context:                   # the frame launch is part of graph F (with dataaug_D_noise: its key draw and the noisy copy too)
+                names += ["fake_B_with_context"] + (["fake_B_with_context_noisy"] if m.d_noise > 0.0 else [])
             st.outs = {k: getattr(m, k) for k in names + (["idt_B", "loss_G_NCE_Y"] if m.opt.alg_cut_nce_idt else [])}
-            with torch.cuda.graph(st.bwd, pool=st.fwd.pool(), capture_error_mode="thread_local"):
+            with torch.cuda.graph(st.bwd, pool=st.fwd.pool(), stream=self.stream("cap_stream"), capture_error_mode="thread_local"):
                 ops.zero_pool_reset(m.device, True)
                 with ops.deferred_wgrads(self.wgrad_stream()):     # the ~190 weight gradients of the generator leave as grouped launches on a forked stream
                     (m.loss_G_tot / its).backward(retain_graph=True)
@@ -284,6 +324,8 @@ class CUTStepDriver:
         finally:                           # passed or failed: the caller's inputs and RNG offset come back, every working copy is stale
             torch.cuda.set_rng_state(rng, m.device)
             m.real_A, m.real_B = keep_inputs
+            if m.context:
+                m.real_A_with_context, m.real_B_with_context = keep_ctx
             for n in nets:
                 n.arena._dirty = True
 
@@ -319,7 +361,8 @@ class CUTStepDriver:
             # BatchNorm statistics are per rank, as in the reference's DDP default -- a module that adds one marks itself and gets the eager path
             m.step_driver_note = "a discriminator module issues a collective in its forward: discriminator half not captured"
             return False
-        key = (tuple(m.real_B.shape), m.real_B.dtype, tuple(m.fake_B.shape), its, float(m.loss_scale))
+        real, fake = m.real_B_D, m.fake_B_D        # with data_online_context_pixels: the framed images, and so are the static operands
+        key = (tuple(real.shape), real.dtype, tuple(fake.shape), its, float(m.loss_scale))
         st = self.d_half.get(key, nets, lambda restore: self._d_capture(side, its, nets, restore))
         if st is None:
             return False
@@ -327,7 +370,7 @@ class CUTStepDriver:
         if m.d_noise > 0.0 or m.d_apa:      # one eager launch ahead of the replay writes the static real operand(s): no copy on top of it
             m.real_D_operands(alts, outs=st.reals if m.d_apa else st.reals[:1])
         else:
-            st.real.copy_(m.real_B)
+            st.real.copy_(real)
         for dst, f in zip(st.fakes, fakes):
             dst.copy_(f)
         st.graph.replay()
@@ -341,8 +384,9 @@ class CUTStepDriver:
 
     def _d_capture(self, side, its, nets, restore):
         m = self.model
-        st = DiscGraph(m.real_B.clone(), [m.fake_B.detach().clone() for _ in nets], torch.cuda.CUDAGraph())
-        st.reals = [st.real] + [m.real_B.clone() for _ in nets[1:]] if m.d_apa else [st.real] * len(nets)
+        real, fake = m.real_B_D, m.fake_B_D
+        st = DiscGraph(real.clone(), [fake.detach().clone() for _ in nets], torch.cuda.CUDAGraph())
+        st.reals = [st.real] + [real.clone() for _ in nets[1:]] if m.d_apa else [st.real] * len(nets)
         with torch.cuda.graph(st.graph, stream=side, capture_error_mode="thread_local"):      # other threads (pinned staging, checkpoint writer) may allocate
             ops.zero_pool_reset(m.device, True)
             st.vals, st.tot = m._d_half_body(st.reals, st.fakes, its)

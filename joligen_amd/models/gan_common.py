@@ -60,7 +60,8 @@ def define_discriminators(model, opt):
             # jg_projd_backbone: "lite0" (tf_efficientnet_lite0, the reference's feature network) | "standin" (tests);
             # jg_projd_pretrained: path of a timm tf_efficientnet_lite0 state_dict (the weights cannot be downloaded here)
             net = ProjectedDiscriminator(getattr(opt, "D_proj_network_type", "efficientnet"), interp=getattr(opt, "D_proj_interp", -1),
-                                         img_size=opt.data_crop_size, backbone=getattr(opt, "jg_projd_backbone", "lite0"),
+                                         # gan_networks.py:349,415: the discriminators see data_crop_size + the context margin
+                                         img_size=opt.data_crop_size + 2 * int(getattr(opt, "data_online_context_pixels", 0) or 0), backbone=getattr(opt, "jg_projd_backbone", "lite0"),
                                          pretrained_path=getattr(opt, "jg_projd_pretrained", ""),
                                          diffusion_aug=bool(getattr(opt, "dataaug_D_diffusion", False)))
         setattr(model, "netD_B_" + d, net)

@@ -966,16 +966,21 @@ def reflect_pad2d(x, pad):
     return _ReflectPadFn.apply(x, pad)
 
 
+def _crop_window(x, top, left, Ho, Wo):
+    """y = x[:, top:top+Ho, left:left+Wo] of a contiguous NHWC tensor (jg_crop2d, adjoint 0), no autograd"""
+    B, H, W, Cc = x.shape
+    y = torch.empty(B, Ho, Wo, Cc, device=x.device, dtype=x.dtype)
+    check(_lib.lib().jg_crop2d(_dt(x), x.data_ptr(), y.data_ptr(), B, H, W, Cc, top, left, Ho, Wo, 0, _st()), "jg_crop2d")
+    return y
+
+
 class _CropFn(JGFunction):
     @staticmethod
     def forward(ctx, x, top, left, Ho, Wo):
         _require_cuda(x)
         x = x.contiguous()
-        B, H, W, Cc = x.shape
-        y = torch.empty(B, Ho, Wo, Cc, device=x.device, dtype=x.dtype)
-        check(_lib.lib().jg_crop2d(_dt(x), x.data_ptr(), y.data_ptr(), B, H, W, Cc, top, left, Ho, Wo, 0, _st()), "jg_crop2d")
-        ctx.cfg = (H, W, top, left)
-        return y
+        ctx.cfg = (x.shape[1], x.shape[2], top, left)
+        return _crop_window(x, top, left, Ho, Wo)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -2083,6 +2088,91 @@ def _dd_check_maps(xs, what):
         if x.dim() != 4 or x.dtype != xs[0].dtype or x.shape[0] != xs[0].shape[0] or not x.is_contiguous() or x.numel() == 0:
             raise TypeError(f"{what}: every map must be a contiguous NHWC tensor of one 16-bit dtype and one batch size, got {tuple(x.shape)} {x.dtype}")
     return n, xs[0].shape[0]
+
+
+# ---- data_online_context_pixels: the loader's image split into crop + surroundings, the frame around the translated crop (csrc/context.hip) --
+def _context_split_check(x, c):
+    _require_cuda(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise TypeError(f"context_split: an fp32 NCHW image is expected, got {tuple(x.shape)} {x.dtype}")
+    if c < 1 or x.shape[2] - 2 * c < 1 or x.shape[3] - 2 * c < 1:
+        raise ValueError(f"context_split: c = {c} leaves no crop inside an image of {tuple(x.shape[2:])} (c >= 1 and size > 2 c are required)")
+
+
+def context_split(x_nchw, c, act_dtype, cpad=None):
+    """set_input with data_online_context_pixels = c (models/base_model.py:389-431) from ONE read of the fp32 NCHW image [B, C, S + 2c, S + 2c]:
+    -> (ctx [B, S + 2c, S + 2c, Cpad], crop [B, S, S, Cpad] = ctx[:, c:-c, c:-c]), 16-bit NHWC, what ops.to_nhwc would write.  No autograd."""
+    c = int(c)
+    _context_split_check(x_nchw, c)
+    x = x_nchw.contiguous()
+    if TORCH_OPS_BOUNDARY:
+        return tuple(torch.ops.jg355.context_split(x, c, act_dtype == torch.float16, int(cpad or 0)))
+    return launch.context_split(x, c, act_dtype, cpad)
+
+
+def _context_frame_check(inner, ctx, c, C, z, key, outs):
+    _require_cuda(inner, ctx, z, key, *(outs or ()))
+    if inner.dim() != 4 or ctx.dim() != 4 or inner.dtype != ctx.dtype or not ctx.is_contiguous():
+        raise TypeError(f"context_frame: inner and ctx must be 16-bit NHWC tensors of one dtype, ctx contiguous (got {tuple(inner.shape)} {inner.dtype}, "
+                        f"{tuple(ctx.shape)} {ctx.dtype})")
+    B, H, W, cpad = ctx.shape
+    if c < 1 or tuple(inner.shape) != (B, H - 2 * c, W - 2 * c, cpad) or H - 2 * c < 1 or W - 2 * c < 1:
+        raise ValueError(f"context_frame: inner {tuple(inner.shape)} is not the window of ctx {tuple(ctx.shape)} at c = {c} (c >= 1)")
+    if not 1 <= C <= cpad:
+        raise ValueError(f"context_frame: 1 <= C <= {cpad} is required (C = {C})")
+    if z is not None and (z.dtype != torch.float32 or tuple(z.shape) != (B, C, H, W) or not z.is_contiguous()):
+        raise TypeError(f"context_frame: z must be contiguous fp32 {(B, C, H, W)}, got {tuple(z.shape)} {z.dtype}")
+    if key is not None and (key.dtype != torch.int32 or key.numel() != 2):
+        raise TypeError("context_frame: key must hold two int32 words")
+    if outs is not None:
+        if len(outs) != 2 or outs[0] is None:
+            raise ValueError("context_frame: outs = (out, out_noisy or None)")
+        for t in outs:
+            if t is not None and (t.dtype != ctx.dtype or tuple(t.shape) != tuple(ctx.shape) or not t.is_contiguous()):
+                raise TypeError(f"context_frame: every output must be contiguous {tuple(ctx.shape)} {ctx.dtype}, got {tuple(t.shape)} {t.dtype}")
+
+
+class _ContextFrameFn(JGFunction):
+    """(out, out_noisy) from one launch; the gradient of `out` with respect to `inner` is its window (jg_crop2d), the frame and the noisy copy
+    carry none"""
+
+    @staticmethod
+    def forward(ctx_, inner, ctx, c, C, sigma, z, key, noise_stream, call, outs, want_noisy):
+        out, noisy = launch.context_frame(inner.contiguous(), ctx, c, C, sigma, z, key, noise_stream, call, *(outs or (None, None)), want_noisy)
+        ctx_.cfg = (c, inner.shape[1], inner.shape[2])
+        if noisy is None:
+            return out, None
+        ctx_.mark_non_differentiable(noisy)
+        return out, noisy
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx_, dout, _dnoisy):
+        c, Hi, Wi = ctx_.cfg
+        return (_crop_window(dout.contiguous(), c, c, Hi, Wi),) + (None,) * 10
+
+
+def context_frame(inner, ctx, c, C, sigma=0.0, z=None, key=None, call=0, outs=None, noise_stream=D_AUG_NOISE_STREAM):
+    """compute_fake_with_context (models/base_model.py:609-636) with the dataaug_D_noise of the framed image folded in (cut_model.py:668-682), on
+    16-bit NHWC tensors: out [B, S + 2c, S + 2c, Cpad] = inner [B, S, S, Cpad] inside the window, ctx on the frame; with sigma != 0 also
+    out_noisy = out + sigma * z over the whole framed image -- z fp32 [B, C, S + 2c, S + 2c] (injected) or None: drawn in the kernel from `key`
+    (d_aug_key) at call index `call`, bit-identical to ops.d_aug(out, C, sigma, key=key, call=call).  outs: (out, out_noisy or None), tensors to
+    write (the static operands of a captured graph), default fresh ones.  Returns (out, out_noisy or None).  Differentiable in `inner` through
+    `out` (the window of the incoming gradient); ctx and out_noisy are detached, as the reference's D inputs are."""
+    c, C, sigma = int(c), int(C), float(sigma)
+    ctx = ctx.detach()
+    _context_frame_check(inner, ctx, c, C, z, key, outs)
+    want_noisy = sigma != 0.0 or (outs is not None and outs[1] is not None)
+    if TORCH_OPS_BOUNDARY:
+        out, noisy = torch.ops.jg355.context_frame(inner, ctx, c, C, sigma, z, key, int(noise_stream), int(call), want_noisy)
+        noisy = noisy.detach() if want_noisy else None
+        if outs is not None:      # the op is functional: the caller's destinations get copies (the gradient still flows through `out`)
+            outs[0].copy_(out.detach())
+            if outs[1] is not None:
+                outs[1].copy_(noisy)
+                noisy = outs[1]
+        return out, noisy
+    return _ContextFrameFn.apply(inner, ctx, c, C, sigma, z, key, int(noise_stream), int(call), None if outs is None else tuple(outs), want_noisy)
 
 
 def _d_diffusion_launch(xs, a, b, t_epl, noise_std, key, call, ts, zs, outs, t_outs):

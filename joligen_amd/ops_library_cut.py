@@ -21,6 +21,7 @@ inputs contiguous, hands fresh zeros to the accumulating kernels and turns a Non
   pixel_loss / pixel_loss_bwd                paired (supervised) and identity L1 / MSE between 16-bit images, both terms in one launch set
   cls_loss                                   train_semantic_cls: cross entropy / MSE / L1 with the device-side gate, gradient and argmax, one launch
   d_aug, apa_update                          dataaug_D_noise + adaptive pseudo augmentation: the discriminators' inputs of a step; the update of p
+  context_split, context_frame / _bwd        data_online_context_pixels: crop + framed image from one read; the translated crop inside its frame (+ D noise)
   d_diffusion / _bwd, d_diffusion_update     dataaug_D_diffusion: the noised backbone features of the projected discriminator; the update of its state
   gan_loss, hinge_loss                       GANLoss (lsgan / vanilla / wgangp) and the projected hinge; return (loss, d loss / d pred)
   spectral_weight / _bwd                     torch.nn.utils.spectral_norm: one power iteration, W / sigma; gradient through 1 / sigma
@@ -622,6 +623,56 @@ def apa_update(pred: T, state: T, n: int, stride: int, target: float, num: float
 @apa_update.register_fake
 def _(pred, state, n, stride, target, num, den):
     return None
+
+
+# ---- data_online_context_pixels: the loader's image split into crop + surroundings; the frame around the translated crop -----------------
+@op("jg355::context_split", mutates_args=())
+def context_split(x: T, c: int, fp16: bool, cpad: int) -> Tuple[T, T]:
+    """ops.context_split as a functional op: fp32 NCHW [B, C, H, W] -> (ctx [B, H, W, Cpad], crop = ctx[:, c:-c, c:-c]), 16-bit NHWC; cpad 0: C
+    rounded up to a multiple of 8.  Not differentiable (the images are data)"""
+    ops._context_split_check(x, c)
+    return launch.context_split(x.contiguous(), c, torch.float16 if fp16 else torch.bfloat16, cpad or None)
+
+
+@context_split.register_fake
+def _(x, c, fp16, cpad):
+    B, C, H, W = x.shape
+    dt, cp = torch.float16 if fp16 else torch.bfloat16, cpad or (C + 7) // 8 * 8
+    return x.new_empty((B, H, W, cp), dtype=dt), x.new_empty((B, H - 2 * c, W - 2 * c, cp), dtype=dt)
+
+
+@op("jg355::context_frame", mutates_args=())
+def context_frame(inner: T, ctx: T, c: int, C: int, sigma: float, z: Optional[T], key: Optional[T], noise_stream: int, call: int,
+                  want_noisy: bool) -> Tuple[T, T]:
+    """ops.context_frame as a functional op: -> (out = inner inside the window of ctx, ctx on the frame; out_noisy = out + sigma z, or an empty
+    tensor unless `want_noisy`)"""
+    ctx = ctx.contiguous()
+    ops._context_frame_check(inner, ctx, c, C, z, key, None)
+    out, noisy = launch.context_frame(inner.contiguous(), ctx, c, C, sigma, z, key, noise_stream, call, want_noisy=want_noisy)
+    return out, noisy if noisy is not None else _z(ctx, ctx.dtype)
+
+
+@context_frame.register_fake
+def _(inner, ctx, c, C, sigma, z, key, noise_stream, call, want_noisy):
+    out = torch.empty_like(ctx, memory_format=torch.contiguous_format)
+    return out, torch.empty_like(out) if want_noisy else ctx.new_empty((0,))
+
+
+@op("jg355::context_frame_bwd", mutates_args=())
+def context_frame_bwd(dout: T, c: int) -> T:
+    """the adjoint of the frame with respect to `inner`: the window dout[:, c:-c, c:-c]"""
+    B, H, W, _ = dout.shape
+    return ops._crop_window(dout.contiguous(), c, c, H - 2 * c, W - 2 * c)
+
+
+@context_frame_bwd.register_fake
+def _(dout, c):
+    B, H, W, Cp = dout.shape
+    return dout.new_empty((B, H - 2 * c, W - 2 * c, Cp))
+
+
+context_frame.register_autograd(lambda ctx, dout, dnoisy: (torch.ops.jg355.context_frame_bwd(dout, ctx.c),) + (None,) * 9,
+                                setup_context=lambda ctx, inputs, output: setattr(ctx, "c", inputs[2]))
 
 
 # ---- dataaug_D_diffusion: noise on the backbone features of the projected discriminator ----------------------------------------------------
