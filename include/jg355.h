@@ -855,7 +855,7 @@ int jg_ema_update(float* ema, const float* p, int64_t n, float beta, jg_stream_t
  * (device array of int64[8]): {src_off, dst_off, dstT_off, Cout, RS, Cin, CoutPad, CinPad}.
  *   w16 [CoutPad][R][S][CinPad]  = cast(p[Cout][R][S][Cin]) zero padded
  *   w16T[CinPad][R][S][CoutPad]  = w16[co][R-1-r][S-1-s][ci]   (input-gradient weights; dstT_off < 0 skips)
- * R, S taken from desc RS = R*65536 + S. */
+ * RS = R * S, the number of taps: the transposed image mirrors the flattened tap index (RS - 1 - rs), which flips r and s at once. */
 int jg_refresh_weights(int dtype, const float* p, void* w16, void* w16T, const int64_t* desc, int nlayers, jg_stream_t s);
 
 /* ---- ViT feature network of the projected discriminator (csrc/vit.hip) ------------------------------------------------------

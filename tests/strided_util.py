@@ -227,3 +227,56 @@ def verify(pair, *, exact=(), approx=None, kernel=None):
                 bad = (~same).reshape(-1, same.shape[-1]).cpu()
                 raise AssertionError(f"output {name!r}: strided launch differs from the contiguous one in {int(bad.sum())} elements; first "
                                      f"(pixel, channel): {bad.nonzero()[:5].tolist()}")
+
+
+Single = namedtuple("Single", "views bufs kernel ret")
+
+
+def run_once(launch, operands, *, tuning=None, device="cpu", guard=3, last_kernel=_default_last_kernel, set_tuning=_default_set_tuning,
+             sync=_default_sync):
+    """One launch on contiguous guarded operands (left = right = 0) under the given tuning switches: run_pair's first half, for tests that
+    compare with a reference instead of a second launch.  Returns Single(views, buffers, kernel after the launch, launch's return)."""
+    prev = {k: set_tuning(k, v) for k, v in (tuning or {}).items()}
+    try:
+        bufs, views = {}, {}
+        for name, op in operands.items():
+            bufs[name], views[name] = make_slice(op.shape, op.dtype, op.seed, left=0, right=0, guard=guard, role=op.role, values=op.values,
+                                                 scale=op.scale, device=device)
+        ret = launch(views)
+        sync()
+        kernel = last_kernel()
+    finally:
+        for k, v in prev.items():
+            set_tuning(k, v)
+    return Single(views, bufs, kernel, ret)
+
+
+def verify_once(single, *, kernel=None):
+    """(a) the launch went to `kernel` (if given); (d) every canary is intact, every role-"out" view fully written, no output holds a NaN"""
+    if kernel is not None:
+        assert single.kernel == kernel, f"expected kernel instance {kernel!r}, got {single.kernel!r}"
+    for name, buf in single.bufs.items():
+        try:
+            assert_canary_intact(buf)
+            if buf.spec.role == "out":
+                assert_fully_written(buf)
+        except AssertionError as e:
+            raise AssertionError(f"operand {name!r}: {e}") from None
+        if buf.spec.role != "in":
+            assert not bool(torch.isnan(single.views[name].float()).any()), f"NaN in output {name!r}"
+
+
+def assert_bit_equal(got, ref, what):
+    """`got` [..., C] equals the float64 `ref` (same shape) rounded to got's dtype, bit for bit, in every element; reports the count and the first
+    few (pixel, channel) positions with got / want"""
+    got = got.detach().cpu().contiguous()
+    want = (ref.detach().cpu() + 0.0).to(got.dtype).contiguous()      # + 0.0: a zero of the reference is +0, as a sum that starts from +0 gives it
+    assert got.shape == want.shape, (what, tuple(got.shape), tuple(want.shape))
+    idt = _INT[got.element_size()]
+    bad = got.view(idt) != want.view(idt)
+    if bool(bad.any()):
+        bad2 = bad.reshape(-1, bad.shape[-1])
+        g2, w2 = got.reshape(bad2.shape), want.reshape(bad2.shape)
+        first = [((p, c), float(g2[p, c]), float(w2[p, c])) for p, c in bad2.nonzero()[:5].tolist()]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ from the exact reference; first ((pixel, channel), got, "
+                             f"want): {first}")

@@ -19,13 +19,17 @@ Two placements per case: "exec" (left offsets multiples of 64 channels, as in th
 A combination the library does not serve on a slice is listed in REFUSED with its reason and asserted as such.
 """
 import math
-from collections import namedtuple
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 import strided_util as su
+from kernel_cases import CONV_ROWS, NSLOT, WG_ROWS, ConvCase, conv_opts, conv_reference, conv_shapes
+from kernel_cases import conv_out_hw as _conv_out_hw
+from kernel_cases import nchw as _nchw
+from kernel_cases import wgrad_opts
+from kernel_cases import wgrad_reference as _wgrad_reference
 from strided_util import Operand
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +38,6 @@ DTYPES = [torch.float16, torch.bfloat16]
 TOL = {torch.float16: 1e-3, torch.bfloat16: 8e-3}
 STATS_BOUND = 1e-5      # fp32 atomics in another order: fused statistics, GroupNorm reductions (test_conv_p64_persistent_kernel)
 WGRAD_BOUND = 2e-5      # weight gradients accumulated across workgroups (comment above HALO_FORCED in test_gpu_0_ops.py)
-NSLOT = 16
 SILU = 1
 
 
@@ -58,14 +61,6 @@ def _rnd(shape, dtype, seed, scale=1.0):
     return (torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale).to(dtype)
 
 
-def _nchw(v):
-    return v.double().cpu().permute(0, 3, 1, 2)
-
-
-def _up2(t_nchw):
-    return t_nchw.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
-
-
 def _pair(launch, operands, kind, tuning=None, fixed=()):
     return su.run_pair(launch, operands, kind=kind, tuning=tuning, device=dev(), fixed=fixed)
 
@@ -78,49 +73,7 @@ def _close(got, ref, tol, what):
 # ======================================================================================================================================
 # jg_conv2d_nt: x, y and res strided; bias; alpha = 0.5, res_scale = 0.7
 # ======================================================================================================================================
-ConvCase = namedtuple("ConvCase", "id inst geo tune opts", defaults=({}, {}))
-G128, G256, G64, G32 = ("conv_nt_glds_kernel<128,128,64,2,2>", "conv_nt_glds_kernel<256,64,64,4,1>", "conv_nt_glds_kernel<64,64,64,2,2>",
-                        "conv_nt_glds_kernel<256,32,64,4,1>")
-NO_SMALL = {"JG_CONV_SMALL_TILE": 0}       # the default tiles at test-sized grids (the automatic choice there is the 64 x 64 tile)
-
-CONV_ROWS = [
-    # geo = (B, H, W, Cin, Cout, R, S, pad, stride)
-    # generic LDS-DMA kernel (CONV_CASES / SPLITK_CASES of test_gpu_0_ops.py)
-    ConvCase("glds128-raggedM", G128, (1, 10, 12, 64, 128, 3, 3, 1, 1), NO_SMALL),
-    ConvCase("glds256x64", G256, (2, 16, 16, 32, 64, 3, 3, 1, 1), NO_SMALL),
-    ConvCase("glds64", G64, (2, 16, 16, 32, 64, 3, 3, 1, 1)),
-    ConvCase("glds256x32-cout8", G32, (1, 208, 208, 16, 8, 3, 3, 1, 1)),      # >= 160 tiles of 256 pixels: the 32-wide tile, unsplit
-    ConvCase("glds-K72", G64, (2, 16, 16, 8, 64, 3, 3, 1, 1)),
-    ConvCase("glds-stride2", G64, (2, 16, 16, 32, 64, 3, 3, 1, 2)),
-    ConvCase("glds-1x1", G128, (2, 12, 12, 64, 192, 1, 1, 0, 1), NO_SMALL),
-    ConvCase("glds-4x4", G64, (1, 9, 9, 16, 32, 4, 4, 1, 1)),
-    ConvCase("glds256x32+splitK", G32 + "+splitK", (4, 7, 7, 512, 8, 4, 4, 1, 1)),
-    ConvCase("glds128+splitK", G128 + "+splitK", (2, 16, 16, 256, 256, 4, 4, 1, 2)),
-    # halo-resident 3x3 kernel: every forced configuration at the HALO_FORCED shapes, then the modes on one shape
-    ConvCase("halo-cfg3", "conv3x3_halo_kernel<256-wide,8 waves>", (2, 32, 32, 192, 256, 3, 3, 1, 1), {"JG_HALO_CFG": 3}),
-    ConvCase("halo-cfg2", "conv3x3_halo_kernel<128-wide,8 waves>", (2, 32, 16, 128, 128, 3, 3, 1, 1), {"JG_HALO_CFG": 2}),
-    ConvCase("halo-cfg4", "conv3x3_halo_kernel<64-wide>", (2, 16, 32, 192, 64, 3, 3, 1, 1), {"JG_HALO_CFG": 4}),
-    ConvCase("halo-cfg1", "conv3x3_halo_kernel<128-wide,4 waves>", (2, 16, 16, 192, 256, 3, 3, 1, 1), {"JG_HALO_CFG": 1}),
-    ConvCase("halo-stats", "conv3x3_halo_kernel<128-wide,4 waves>", (2, 16, 16, 192, 256, 3, 3, 1, 1), {"JG_HALO_CFG": 1}, dict(stats=True)),
-    ConvCase("halo-reflect", "conv3x3_halo_kernel<128-wide,4 waves>", (2, 16, 32, 128, 128, 3, 3, 1, 1), {}, dict(pad_mode=1)),
-    ConvCase("halo-x_up", "conv3x3_halo_kernel<128-wide,4 waves>", (2, 16, 32, 128, 128, 3, 3, 1, 1), {}, dict(x_mode=1)),
-    ConvCase("halo-subpixel", "conv3x3_halo_kernel<subpixel>", (1, 32, 64, 128, 128, 3, 3, 1, 1), {}, dict(x_mode=2)),
-    ConvCase("halo-y_pool", "conv3x3_halo_kernel<128-wide,4 waves>", (2, 16, 32, 128, 128, 3, 3, 1, 1), {}, dict(y_mode=1, bias=False, res=False)),
-    ConvCase("halo-res_up", "conv3x3_halo_kernel<128-wide,4 waves>", (2, 16, 32, 128, 128, 3, 3, 1, 1), {}, dict(res_mode=1)),
-    # persistent Cin == 64 kernel, forced (first four rows of P64_CASES), fused statistics into a wider row
-    ConvCase("p64-2streams", "conv3x3_p64_kernel", (2, 32, 48, 64, 64, 3, 3, 1, 1), {"JG_PERSIST64": 2}, dict(res=False, stats=True)),
-    ConvCase("p64-5streams", "conv3x3_p64_kernel", (3, 64, 64, 64, 128, 3, 3, 1, 1), {"JG_PERSIST64": 5}, dict(stats=True)),
-    ConvCase("p64-3blocks", "conv3x3_p64_kernel", (1, 48, 32, 64, 192, 3, 3, 1, 1), {"JG_PERSIST64": 3}, dict(stats=True)),
-    ConvCase("p64-1tile", "conv3x3_p64_kernel", (1, 16, 16, 64, 64, 3, 3, 1, 1), {"JG_PERSIST64": 7}, dict(stats=True)),
-    # streaming kernels (>= 65536 pixels)
-    ConvCase("1x1-stream", "conv1x1_stream_kernel", (1, 256, 256, 64, 128, 1, 1, 0, 1)),
-    ConvCase("c8-stem", "conv3x3_c8_stream_kernel", (1, 256, 256, 8, 64, 3, 3, 1, 1), {}, dict(fixed=("x",))),
-    ConvCase("c8-stem-stats", "conv3x3_c8_stream_kernel", (1, 256, 256, 8, 128, 3, 3, 1, 1), {}, dict(fixed=("x",), stats=True)),
-    # halo-resident few-output-channel kernels: no residual operand in these kernels
-    ConvCase("kxk-7x7", "conv_kxk_halo_kernel<7x7>", (3, 80, 80, 32, 8, 7, 7, 3, 1), {}, dict(res=False)),
-    ConvCase("kxk-1x7", "conv_kxk_halo_kernel<1x7>", (1, 134, 134, 64, 32, 1, 7, 0, 1), {}, dict(res=False)),
-    ConvCase("kxk-3x3", "conv_kxk_halo_kernel<3x3>", (4, 256, 256, 64, 8, 3, 3, 1, 1), {}, dict(res=False)),
-]
+# ConvCase / CONV_ROWS: tests/kernel_cases.py (one list of kernel instances, shared with the exact-integer tests)
 
 # combinations the library does not serve on a channel slice; each is asserted in test_refused_combinations
 REFUSED = [
@@ -130,22 +83,15 @@ REFUSED = [
 ]
 
 
-def _conv_out_hw(H, W, R, S, pad, stride):
-    return (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
-
-
 def _conv_problem(case, dtype, strided_x_for_c8=False):
     """operands, launch and float64 reference of one ConvCase"""
     from joligen_amd import _lib, ops
 
     B, H, W, Cin, Cout, R, S, pad, stride = case.geo
-    o = dict(bias=True, res=True, stats=False, pad_mode=0, x_mode=0, y_mode=0, res_mode=0, fixed=())
-    o.update(case.opts)
+    o = conv_opts(case)
     Ho, Wo = _conv_out_hw(H, W, R, S, pad, stride)
     d = dev()
-    xs = (B, H // 2, W // 2, Cin) if o["x_mode"] else (B, H, W, Cin)
-    ys = (B, Ho // 2, Wo // 2, Cout) if o["y_mode"] else (B, Ho, Wo, Cout)
-    rs = (B, Ho // 2, Wo // 2, Cout) if o["res_mode"] else (B, Ho, Wo, Cout)
+    xs, ys, rs = conv_shapes(case)
     operands = {"x": Operand(xs, dtype, "in", 1), "y": Operand(ys, dtype, "out")}
     if o["res"]:
         operands["res"] = Operand(rs, dtype, "in", 4)
@@ -170,22 +116,7 @@ def _conv_problem(case, dtype, strided_x_for_c8=False):
                     res_mode=o["res_mode"], x_mode=o["x_mode"], y_mode=o["y_mode"])
 
     def reference(v):
-        x = _nchw(v["x"])
-        if o["x_mode"]:
-            x = _up2(x)
-        if o["pad_mode"]:
-            y = F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), wref.permute(0, 3, 1, 2), None, stride, 0)
-        else:
-            y = F.conv2d(x, wref.permute(0, 3, 1, 2), None, stride, pad)
-        y = 0.5 * y
-        if o["y_mode"]:
-            y = 4 * F.avg_pool2d(y, 2)
-        if bias is not None:
-            y = y + bias.double().view(1, -1, 1, 1)
-        if o["res"]:
-            r = _nchw(v["res"])
-            y = y + 0.7 * (_up2(r) if o["res_mode"] else r)
-        return y
+        return conv_reference(v["x"], v.get("res"), wref, bias, case, 0.5, 0.7)
 
     return operands, launch, reference, o
 
@@ -334,40 +265,6 @@ def test_reflect_dgrad_border_on_channel_slices(kind, dtype):
 # ======================================================================================================================================
 # jg_conv2d_wgrad_tn: dy and x strided; dbias
 # ======================================================================================================================================
-WgCase = namedtuple("WgCase", "id inst geo splitk tune opts", defaults=({}, {}))
-WG_ROWS = [
-    # geo = (B, H, W, Cin, Cout, R, S, pad, stride); splitk 1 + store = JG_OUT_STORE_F32 (plain stores: bit-exact), otherwise fp32 atomics
-    WgCase("tr1-1x1-store", "wgrad_tn_tr_kernel<1>", (2, 20, 12, 64, 64, 1, 1, 0, 1), 1, {"JG_WGRAD_VARIANT": 2}, dict(store=True)),
-    WgCase("tr1-1x1-splitk3", "wgrad_tn_tr_kernel<1>", (2, 20, 12, 64, 64, 1, 1, 0, 1), 3, {"JG_WGRAD_VARIANT": 2}),
-    WgCase("tr2-3x3-s2-store", "wgrad_tn_tr_kernel<2>", (2, 17, 17, 32, 160, 3, 3, 1, 2), 1, {"JG_WGRAD_VARIANT": 2}, dict(store=True)),
-    WgCase("tr1-3x3-ragged-onestep", "wgrad_tn_tr_kernel<1>", (1, 9, 7, 24, 40, 3, 3, 1, 1), 1, {"JG_WGRAD_VARIANT": 2}, dict(store=True)),
-    WgCase("big-1x1-ragged", "wgrad_tn_big_kernel", (3, 64, 48, 256, 320, 1, 1, 0, 1), 4, {}, dict(real_cout=316)),
-    WgCase("big-4x4-s2", "wgrad_tn_big_kernel", (2, 128, 128, 32, 256, 4, 4, 1, 2), 2),
-    WgCase("halo-cfg1", "wgrad3x3_halo_kernel<16 rows,64 co>", (2, 32, 32, 64, 128, 3, 3, 1, 1), 1, {"JG_WGRAD_HALO_CFG": 1}),
-    WgCase("halo-cfg2", "wgrad3x3_halo_kernel<8 rows,128 co>", (2, 32, 32, 128, 128, 3, 3, 1, 1), 1, {"JG_WGRAD_HALO_CFG": 2}),
-    WgCase("halo-cfg3", "wgrad3x3_halo_kernel<8 rows,64 co,4 waves>", (2, 32, 32, 128, 64, 3, 3, 1, 1), 1, {"JG_WGRAD_HALO_CFG": 3}),
-    WgCase("halo-cfg4", "wgrad3x3_halo_kernel<8 rows,32 co,4 waves>", (3, 16, 48, 64, 128, 3, 3, 1, 1), 1, {"JG_WGRAD_HALO_CFG": 4}),
-    WgCase("sw-cfg6", "wgrad3x3_sw_kernel<16 rows,64 co>", (3, 16, 48, 192, 64, 3, 3, 1, 1), 1, {"JG_WGRAD_HALO_CFG": 6}),
-    WgCase("halo-narrow", "wgrad3x3_halo_kernel<16 rows,<64 co>", (4, 256, 256, 64, 8, 3, 3, 1, 1), 1, {}, dict(real_cout=3)),
-    WgCase("halo-reflect", "wgrad3x3_halo_kernel<16 rows,64 co>", (2, 16, 32, 128, 64, 3, 3, 1, 1), 1, {}, dict(pad_mode=1)),
-    WgCase("halo-x_up", "wgrad3x3_halo_kernel<16 rows,64 co>", (2, 16, 32, 128, 64, 3, 3, 1, 1), 1, {}, dict(x_mode=1)),
-    WgCase("kxk-7x7", "wgrad_kxk_halo_kernel<7x7,2 tap rows>", (4, 128, 128, 64, 8, 7, 7, 3, 1), 1, {}, dict(real_cout=3)),
-    WgCase("kxk-1x7", "wgrad_kxk_halo_kernel<1x7>", (1, 256, 262, 64, 32, 1, 7, 0, 1), 1),
-]
-
-
-def _wgrad_reference(x, dy, geo, o):
-    B, H, W, Cin, Cout, R, S, pad, stride = geo
-    xin = _nchw(x)
-    if o.get("x_mode"):
-        xin = _up2(xin)
-    if o.get("pad_mode"):
-        xin, pad = F.pad(xin, (1, 1, 1, 1), mode="reflect"), 0
-    wr = torch.zeros(Cout, Cin, R, S, dtype=torch.float64, requires_grad=True)
-    F.conv2d(xin, wr, None, stride, pad).backward(_nchw(dy))
-    return wr.grad.permute(0, 2, 3, 1).reshape(Cout, -1), dy.double().cpu().sum((0, 1, 2))
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["fp16", "bf16"])
 @pytest.mark.parametrize("kind", su.PLACEMENTS)
 @pytest.mark.parametrize("case", WG_ROWS, ids=[c.id for c in WG_ROWS])
@@ -375,8 +272,7 @@ def test_wgrad_tn_on_channel_slices(case, kind, dtype):
     from joligen_amd import _lib, ops
 
     B, H, W, Cin, Cout, R, S, pad, stride = case.geo
-    o = dict(store=False, real_cout=Cout, pad_mode=0, x_mode=0)
-    o.update(case.opts)
+    o = wgrad_opts(case)
     Ho, Wo = _conv_out_hw(H, W, R, S, pad, stride)
     real = o["real_cout"]
     dyv = _rnd((B, Ho, Wo, Cout), dtype, 12)
